@@ -30,6 +30,11 @@ Rank 0 prints ONE JSON line.  `value` = all QPs solved by all ranks / max-over-r
 `hbm_algorithmic_x` keeps the streaming-model GB/s figure (may exceed the HBM peak for the resident kernels: the
 matrices are not re-read).  `cpu_baseline` times the oracle on the host cores in child processes started BEFORE this
 process touches the GPU.
+
+A plain run only sets up, warms up, times the --steps steps and prints the line (`value`, `ms_per_step`, ...).
+`--full` adds the legs the headline does not need: `cpu_baseline`, `value_with_history` and `roofline`.
+`--dump-outputs DIR` writes the Results of the last timed step as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -65,7 +70,7 @@ def parse():
     ap.add_argument("--n-ineq", type=int, default=275)
     ap.add_argument("--eps-abs", type=float, default=1e-3)
     ap.add_argument("--precision", choices=["f32", "f64"], default="f32")
-    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="budget of the cpu_baseline leg, split over its modes (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=24.0, help="--full: budget of the cpu_baseline leg, split over its modes (0 = skip)")
     ap.add_argument("--seed0", type=int, default=0)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--kernel", default="auto", help="C-ABI kernel request (auto | generic | resident | wave | mfma)")
@@ -84,7 +89,11 @@ def parse():
                     "matrix as the reference builds them (default: a window of 5 with exact continuation)")
     ap.add_argument("--fresh-batches", type=int, default=4, help="distinct synthetic batches (one handle each) the timed steps "
                     "rotate through; every solve runs without dispatch history")
-    ap.add_argument("--history-steps", type=int, default=5, help="steps of the separately reported with-history leg (0 = skip)")
+    ap.add_argument("--history-steps", type=int, default=5, help="--full: steps of the separately reported with-history leg (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the cpu_baseline leg, the "
+                    "with-history leg and the roofline figures (default: set up, warm up, time --steps, print the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the Results of the last "
+                    "timed solve() as DIR/<name>.npy (float32/float64; a fixed sample of instances beyond 64 MB)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)     # internal: child process of the cpu_baseline leg
     a = ap.parse_args()
     if a.workload == "c4":
@@ -228,6 +237,88 @@ def pmc_traffic(kernel, args, kern_s):
     return nbytes / kern_s / 1e9, "profiles/" + name + " (bytes per launch / this run's kernel time)"
 
 
+def roofline(kernel, args, n, m, esz, blocks, rank_iters_max, kern_avg_s, cold_ms):
+    """--full: the ADMM kernel priced against the roof that binds it (module docstring)."""
+    # algorithmic work per launch (one rank's launch: the slowest rank's time against the largest rank's work): SURVEY.md 8(d)
+    b_iter = esz * (n * n + m * n)
+    f_iter = 2 * n * n + 4 * m * n
+    alg_bytes = rank_iters_max * b_iter
+    alg_flops = rank_iters_max * f_iter
+    hbm_gbs = alg_bytes / kern_avg_s / 1e9
+    tf = alg_flops / kern_avg_s / 1e12
+    traffic, traffic_src = pmc_traffic(kernel, args, kern_avg_s)
+    kname = "k_admm_%s" % {"resident2": "res2", "resident64": "res64"}.get(kernel, kernel)
+    if kernel == "mfma":
+        roof = {"bound": "mfma", "achieved": tf, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP32_MFMA_PEAK_TFLOPS,
+                "note": "dense algorithmic flops 2n^2+4mn per instance-iteration; the kernel skips all-zero operand groups of the "
+                        "block-triangular MPC matrices, so it executes fewer"}
+    elif kernel in ("mfmal", "mfmad"):
+        # streamed-operand MFMA kernel: the work is the NON-ZERO 16 x 16 blocks of A (twice: A' nu and A dx) and H plus the
+        # dense K -- 512 flops per block and instance-iteration (every block is 4 v_mfma_f32_16x16x4_f32 over 16 instances)
+        bl = 2 * blocks[0] + blocks[1] + blocks[2]
+        tfb = rank_iters_max * bl * 512.0 / kern_avg_s / 1e12
+        mpeak = FP32_MFMA_PEAK_TFLOPS if kernel == "mfmal" else FP64_MFMA_PEAK_TFLOPS
+        roof = {"bound": "mfma", "achieved": tfb, "peak": mpeak, "unit": "TFLOP/s", "frac": tfb / mpeak,
+                "note": "block-sparse algorithmic flops: 512 per non-zero 16x16 block of A (x2), H and the dense K = %d blocks per "
+                        "instance-iteration (the dense count 2n^2+4mn would be %.1fx that); operands stream from L2, "
+                        "%d KB per block and 16 instances" % (bl, f_iter / (bl * 512.0), esz // 4),
+                "blocks_per_iteration": bl, "l2_operand_gbs": rank_iters_max / 16.0 * bl * 256.0 * esz / kern_avg_s / 1e9}
+    elif kernel == "mfma16":
+        # three bf16 MFMAs per product term pair: the executed matrix flops are 3x the algorithmic ones; priced in ALGORITHMIC
+        # flops against the dense bf16 matrix peak (the kernel is bound by its VALU / LDS phases, not by this roof)
+        roof = {"bound": "mfma", "achieved": tf, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / BF16_MFMA_PEAK_TFLOPS,
+                "note": "algorithmic flops 2n^2+4mn per instance-iteration against the dense bf16 MFMA peak; operands are two bf16 "
+                        "planes and a product is three v_mfma_f32_16x16x32_bf16 (executed matrix flops = 3x + padding); the "
+                        "kernel's time is VALU / LDS latency of its row and column phases (DESIGN.md section 4)",
+                "frac_of_fp32_mfma_peak": tf / FP32_MFMA_PEAK_TFLOPS}
+    elif kernel == "generic":
+        roof = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_gbs / HBM_PEAK_GBS}
+    else:
+        peak = FP32_VALU_PEAK_TFLOPS if args.precision == "f32" else FP64_VALU_PEAK_TFLOPS
+        roof = {"bound": "valu", "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak,
+                "note": "A and K live in registers for the whole solve; the binding roof is %s vector FMA issue.  `traffic` "
+                        "(HBM, PMC) is ~2.5x the compulsory bytes of a launch (the padded lane-linear A / K / H images are "
+                        "larger than the matrices, and K is re-read at every rho move) and still < 10 %% of the HBM peak: "
+                        "irrelevant to the bound" % args.precision}
+    roof.update({"traffic": traffic, "traffic_unit": "GB/s (HBM, PMC)", "traffic_source": traffic_src,
+                 "kernel": kname, "kernel_ms": kern_avg_s * 1e3,
+                 "algorithmic_flops_per_launch": alg_flops, "algorithmic_bytes_per_launch": alg_bytes,
+                 "hbm_algorithmic_gbs": hbm_gbs, "hbm_algorithmic_x": hbm_gbs / HBM_PEAK_GBS})
+    if cold_ms is not None:
+        roof["kernel_ms_cold_process"] = cold_ms      # the very first launch of the process (code-object load included)
+    return roof
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(res, outdir, suffix="", cap=DUMP_CAP_BYTES):
+    """Write what a caller of the timed solve() receives -- the batched Results: x, z, y and the per-instance info
+    tensors -- as outdir/<name><suffix>.npy.  Floating arrays keep their dtype (float32 / float64), integer ones
+    (iter, status_code, rho_ind) become float64 (exact).  Every array has one row per instance; when all of them
+    together exceed `cap` bytes, the same seeded sample of rows is kept in each and `instance_index` lists it."""
+    info = res.info
+    named = {"x": res.x, "z": res.z, "y": res.y, "iter": info.iter, "status_code": info.status_code,
+             "rho_ind": info.rho_ind, "obj_val": info.obj_val, "pri_res": info.pri_res, "dua_res": info.dua_res,
+             "rho_estimate": info.rho_estimate}
+    host = {}
+    for k, t in named.items():
+        a = t.detach().cpu().numpy()
+        host[k] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    rows = host["x"].shape[0]
+    row_bytes = sum(a.nbytes for a in host.values()) // rows
+    if rows * row_bytes > cap:
+        keep = cap // (row_bytes + 8)
+        idx = np.sort(np.random.RandomState(0).choice(rows, keep, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["instance_index"] = idx.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(outdir, k + suffix + ".npy"), np.ascontiguousarray(a))
+    return sorted(host)
+
+
 def main():
     args = parse()
     if args.cpu_worker:
@@ -236,7 +327,7 @@ def main():
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     rank_env = int(os.environ.get("RANK", "0"))
     cpu = None
-    if world_env == 1 and args.cpu_seconds > 0:
+    if args.full and world_env == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args)          # child processes, finished before this process initialises the GPU
 
     # ---- synthetic inputs: `nb` DISTINCT batches per rank, drawn before the GPU is touched (the generator forks workers).
@@ -336,6 +427,8 @@ def main():
         outs.append((res.info.iter, res.info.status_code))
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:             # before the with-history leg, whose solves may overwrite the Results object `res`
+        dump_outputs(res, args.dump_outputs, "" if world_env == 1 else "_rank%d" % rank_env)
 
     sum_iters = float(sum(float(it.to(torch.float64).sum()) for it, _ in outs)) / max(1, args.steps)     # per step
     solved = float(sum(float((sc == 0).sum()) for _, sc in outs)) / max(1, args.steps)
@@ -343,7 +436,7 @@ def main():
     # ---- second, separately reported leg: the SAME batch solved again and again with the longest-first dispatch order
     # learnt from the previous solve (closed loops, parameter sweeps); not `value`
     hist = None
-    if args.history_steps > 0:
+    if args.full and args.history_steps > 0:
         mdl = models[0]
         mdl.dispatch_history(True)
         for _ in range(2):
@@ -370,15 +463,7 @@ def main():
     if rank == 0:
         step_s = elapsed / args.steps
         value = tot_qps / step_s
-        # algorithmic work per launch (one rank's launch: the slowest rank's time against the largest rank's work): SURVEY.md 8(d)
-        b_iter = esz * (n * n + m * n)
-        f_iter = 2 * n * n + 4 * m * n
-        alg_bytes = rank_iters_max * b_iter
-        alg_flops = rank_iters_max * f_iter
-        hbm_gbs = alg_bytes / kern_avg_s / 1e9
-        tf = alg_flops / kern_avg_s / 1e12
         kernel = models[0].kernel
-        traffic, traffic_src = pmc_traffic(kernel, args, kern_avg_s)
         per = "/GPU" if args.scaling == "weak" else " total"
         fresh = ("%d distinct batches in rotation, every solve without dispatch history (= first solve of a fresh handle)" % nb)
         if args.workload == "mpc":
@@ -390,45 +475,6 @@ def main():
             wl = ("batch=%d%s random dense QPs n=%d m=%d (n_eq=%d), feasible rand_qp seeds %d.., eps_abs=%g, cold "
                   "start, reference defaults; %s" % (args.batch, per, n, m, args.n_eq, args.seed0, args.eps_abs, fresh))
             metric = "QP solves/sec (batch=%d random dense QPs n=%d m=%d)" % (args.batch, n, m)
-        kname = "k_admm_%s" % {"resident2": "res2", "resident64": "res64"}.get(kernel, kernel)
-        if kernel == "mfma":
-            roof = {"bound": "mfma", "achieved": tf, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / FP32_MFMA_PEAK_TFLOPS,
-                    "note": "dense algorithmic flops 2n^2+4mn per instance-iteration; the kernel skips all-zero operand groups of the "
-                            "block-triangular MPC matrices, so it executes fewer"}
-        elif kernel in ("mfmal", "mfmad"):
-            # streamed-operand MFMA kernel: the work is the NON-ZERO 16 x 16 blocks of A (twice: A' nu and A dx) and H plus the
-            # dense K -- 512 flops per block and instance-iteration (every block is 4 v_mfma_f32_16x16x4_f32 over 16 instances)
-            bl = 2 * blocks[0] + blocks[1] + blocks[2]
-            tfb = rank_iters_max * bl * 512.0 / kern_avg_s / 1e12
-            mpeak = FP32_MFMA_PEAK_TFLOPS if kernel == "mfmal" else FP64_MFMA_PEAK_TFLOPS
-            roof = {"bound": "mfma", "achieved": tfb, "peak": mpeak, "unit": "TFLOP/s", "frac": tfb / mpeak,
-                    "note": "block-sparse algorithmic flops: 512 per non-zero 16x16 block of A (x2), H and the dense K = %d blocks per "
-                            "instance-iteration (the dense count 2n^2+4mn would be %.1fx that); operands stream from L2, "
-                            "%d KB per block and 16 instances" % (bl, f_iter / (bl * 512.0), esz // 4),
-                    "blocks_per_iteration": bl, "l2_operand_gbs": rank_iters_max / 16.0 * bl * 256.0 * esz / kern_avg_s / 1e9}
-        elif kernel == "mfma16":
-            # three bf16 MFMAs per product term pair: the executed matrix flops are 3x the algorithmic ones; priced in ALGORITHMIC
-            # flops against the dense bf16 matrix peak (the kernel is bound by its VALU / LDS phases, not by this roof)
-            roof = {"bound": "mfma", "achieved": tf, "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / BF16_MFMA_PEAK_TFLOPS,
-                    "note": "algorithmic flops 2n^2+4mn per instance-iteration against the dense bf16 MFMA peak; operands are two bf16 "
-                            "planes and a product is three v_mfma_f32_16x16x32_bf16 (executed matrix flops = 3x + padding); the "
-                            "kernel's time is VALU / LDS latency of its row and column phases (DESIGN.md section 4)",
-                    "frac_of_fp32_mfma_peak": tf / FP32_MFMA_PEAK_TFLOPS}
-        elif kernel == "generic":
-            roof = {"bound": "hbm", "achieved": hbm_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm_gbs / HBM_PEAK_GBS}
-        else:
-            peak = FP32_VALU_PEAK_TFLOPS if args.precision == "f32" else FP64_VALU_PEAK_TFLOPS
-            roof = {"bound": "valu", "achieved": tf, "peak": peak, "unit": "TFLOP/s", "frac": tf / peak,
-                    "note": "A and K live in registers for the whole solve; the binding roof is %s vector FMA issue.  `traffic` "
-                            "(HBM, PMC) is ~2.5x the compulsory bytes of a launch (the padded lane-linear A / K / H images are "
-                            "larger than the matrices, and K is re-read at every rho move) and still < 10 %% of the HBM peak: "
-                            "irrelevant to the bound" % args.precision}
-        roof.update({"traffic": traffic, "traffic_unit": "GB/s (HBM, PMC)", "traffic_source": traffic_src,
-                     "kernel": kname, "kernel_ms": kern_avg_s * 1e3,
-                     "algorithmic_flops_per_launch": alg_flops, "algorithmic_bytes_per_launch": alg_bytes,
-                     "hbm_algorithmic_gbs": hbm_gbs, "hbm_algorithmic_x": hbm_gbs / HBM_PEAK_GBS})
-        if cold_ms is not None:
-            roof["kernel_ms_cold_process"] = cold_ms      # the very first launch of the process (code-object load included)
         out = {
             "metric": metric,
             "value": value,
@@ -453,13 +499,14 @@ def main():
             "setup_s": setup_max,
             "setup_plus_solve_qps": tot_qps / (setup_max + step_s),
             "input_generation_s": t_gen,
-            "roofline": roof,
         }
+        if args.full:
+            roof = out["roofline"] = roofline(kernel, args, n, m, esz, blocks, rank_iters_max, kern_avg_s, cold_ms)
         if hist_step > 0:
             out["value_with_history"] = tot_qps / hist_step
             out["with_history"] = {"ms_per_step": hist_step * 1e3, "kernel_ms": hist_kern * 1e3,
                                    "steps": args.history_steps,
-                                   "roofline_frac": (hist_iters * f_iter / hist_kern / 1e12) /
+                                   "roofline_frac": (hist_iters * (2 * n * n + 4 * m * n) / hist_kern / 1e12) /
                                                     (roof["peak"] if roof["unit"] == "TFLOP/s" else float("nan")),
                                    "note": "one batch solved repeatedly, workgroups issued longest-first by the previous solve's "
                                            "iteration counts; NOT the headline"}

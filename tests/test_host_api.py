@@ -160,5 +160,38 @@ def test_bench_cpu_baseline_leg_runs_without_a_gpu():
         sys.argv = ["bench.py"]
         a = bench.parse()
         assert (a.batch, a.n, a.n_eq + a.n_ineq, a.precision, a.gpus) == (4096, 100, 300, "f32", 1)
+        assert not a.full and a.dump_outputs is None            # a plain run: no extra legs, nothing written
     finally:
         sys.argv = old
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the Results of a batched solve as .npy files, float dtypes kept, integer info as float64;
+    above the byte cap the same seeded rows of every array, listed in instance_index."""
+    import sys
+    from types import SimpleNamespace
+    sys.path.insert(0, REPO)
+    import bench
+    B, n, m = 40, 3, 5
+    rs = np.random.RandomState(1)
+    info = SimpleNamespace(iter=torch.arange(B, dtype=torch.int32), status_code=torch.zeros(B, dtype=torch.int32),
+                           rho_ind=torch.full((B,), 7, dtype=torch.int32), obj_val=torch.from_numpy(rs.randn(B)),
+                           pri_res=torch.from_numpy(rs.rand(B)), dua_res=torch.from_numpy(rs.rand(B)),
+                           rho_estimate=torch.from_numpy(rs.rand(B)))
+    res = SimpleNamespace(x=torch.from_numpy(rs.randn(B, n).astype(np.float32)), z=torch.from_numpy(rs.randn(B, m).astype(np.float32)),
+                          y=torch.from_numpy(rs.randn(B, m).astype(np.float32)), info=info)
+    names = bench.dump_outputs(res, str(tmp_path / "all"))
+    assert "instance_index" not in names
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in names}
+    assert got["x"].dtype == np.float32 and np.array_equal(got["x"], res.x.numpy())
+    assert got["iter"].dtype == np.float64 and np.array_equal(got["iter"], np.arange(B))
+    assert got["obj_val"].dtype == np.float64 and got["y"].shape == (B, m)
+    row = 4 * (n + 2 * m) + 8 * 7
+    for d in ("a", "b"):
+        bench.dump_outputs(res, str(tmp_path / d), cap=10 * row)
+    idx = np.load(str(tmp_path / "a" / "instance_index.npy"))
+    assert np.array_equal(idx, np.load(str(tmp_path / "b" / "instance_index.npy")))      # fixed sample
+    assert 0 < len(idx) < 10 and np.all(np.diff(idx) > 0)
+    assert sum(np.load(str(p)).nbytes for p in (tmp_path / "a").iterdir()) <= 10 * row
+    assert np.array_equal(np.load(str(tmp_path / "a" / "z.npy")), res.z.numpy()[idx.astype(int)])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "iter.npy")), idx)

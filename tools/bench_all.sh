@@ -4,13 +4,13 @@ set -e
 OUT=${1:-gpurun_out/bench_all}
 CPU=${2:-0}
 mkdir -p $OUT
-python3 bench.py --cpu-seconds $CPU > $OUT/bench_resident2.json 2> $OUT/bench_resident2.err
-python3 bench.py --cpu-seconds 0 --precision f64 > $OUT/bench_resident64.json 2> $OUT/bench_resident64.err
-python3 bench.py --cpu-seconds 0 --workload c4 > $OUT/bench_wave.json 2> $OUT/bench_wave.err
-python3 bench.py --cpu-seconds 0 --workload mpc > $OUT/bench_mfma.json 2> $OUT/bench_mfma.err
-python3 bench.py --cpu-seconds 0 --workload mpc --tile bf16 > $OUT/bench_mfma16.json 2> $OUT/bench_mfma16.err
-python3 bench.py --cpu-seconds 0 --workload mpc --mpc-form sparse > $OUT/bench_mfmal.json 2> $OUT/bench_mfmal.err
-python3 bench.py --cpu-seconds 0 --workload mpc --precision f64 > $OUT/bench_mfmad.json 2> $OUT/bench_mfmad.err
+python3 bench.py --full --cpu-seconds $CPU > $OUT/bench_resident2.json 2> $OUT/bench_resident2.err
+python3 bench.py --full --cpu-seconds 0 --precision f64 > $OUT/bench_resident64.json 2> $OUT/bench_resident64.err
+python3 bench.py --full --cpu-seconds 0 --workload c4 > $OUT/bench_wave.json 2> $OUT/bench_wave.err
+python3 bench.py --full --cpu-seconds 0 --workload mpc > $OUT/bench_mfma.json 2> $OUT/bench_mfma.err
+python3 bench.py --full --cpu-seconds 0 --workload mpc --tile bf16 > $OUT/bench_mfma16.json 2> $OUT/bench_mfma16.err
+python3 bench.py --full --cpu-seconds 0 --workload mpc --mpc-form sparse > $OUT/bench_mfmal.json 2> $OUT/bench_mfmal.err
+python3 bench.py --full --cpu-seconds 0 --workload mpc --precision f64 > $OUT/bench_mfmad.json 2> $OUT/bench_mfmad.err
 python3 - <<PY
 import json
 for t in ["resident2", "resident64", "wave", "mfma", "mfma16", "mfmal", "mfmad"]:

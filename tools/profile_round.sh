@@ -8,7 +8,7 @@ OUT=gpurun_out/prof_$R
 mkdir -p $OUT
 run_stats () {  # tag, bench args...
   local tag=$1; shift
-  rocprofv3 --kernel-trace --stats -d $OUT/stats_$tag --output-format csv -- python3 bench.py --cpu-seconds 0 --steps 5 --warmup 2 "$@" > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
+  rocprofv3 --kernel-trace --stats -d $OUT/stats_$tag --output-format csv -- python3 bench.py --full --cpu-seconds 0 --steps 5 --warmup 2 "$@" > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err
   find $OUT/stats_$tag -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_$tag.csv \;
   echo "stats $tag done"
 }
