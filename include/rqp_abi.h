@@ -84,6 +84,11 @@ enum rqp_status {
                                        the reference's)                                                        */
     RQP_STATUS_PRIMAL_INFEASIBLE = 3, /* "primal_infeasible": certificate found (check_infeasibility)          */
     RQP_STATUS_DUAL_INFEASIBLE = 4,   /* "dual_infeasible"                                                     */
+    RQP_STATUS_WINDOW_PASSES = 5,   /* "window_passes_exhausted": a windowed handle under rqp_set_window_passes(P >= 1)
+                                       whose instance still waited for a re-window after the last of the P passes.
+                                       x, z, lam are its exact state at the stop, iter the iterations run so far,
+                                       rho_ind / rho_estimate as at the stop; pri_res, dua_res, obj_val are NaN (not
+                                       evaluated).  The next solve continues it like any other instance.           */
     RQP_STATUS_UNSOLVED = -1        /* never solved          */
 };
 
@@ -111,7 +116,7 @@ enum {
                                  index leaves its window exits with its exact state, rqp_solve re-factors a window around
                                  the new index and continues it -- results are bit-identical to the full ladder, setup and
                                  workspace shrink by ~3x, and rqp_solve synchronises `stream` once per pass (it cannot be
-                                 captured into a HIP graph: use this flag there).                                    */
+                                 captured into a HIP graph: use this flag there, or rqp_set_window_passes).          */
 };
 
 /* Settings of classes.py:32-65 that reach the device (same names, same defaults). */
@@ -270,6 +275,21 @@ int rqp_get_dispatch(rqp_handle* h, int32_t* order, int32_t* last_iter, int32_t*
  * (see RQP_FLAG_FULL_LADDER); wbase (device int32 [batch], NULL to skip; windowed handles only) receives the
  * ladder index of slot 0 of every instance's window.  For tests.                                        */
 int rqp_get_window(rqp_handle* h, int32_t* slots, int32_t* wbase, void* stream);
+
+/* Fixed-pass window protocol of a windowed handle (see RQP_FLAG_FULL_LADDER).  passes = 0 (default): rqp_solve
+ * reads the count of instances that left their window after every pass and synchronises `stream`; it refuses
+ * HIP-graph capture (RQP_ERR_UNSUPPORTED).  passes = P >= 1: rqp_solve enqueues the first launch, then P
+ * continuation passes (re-window, re-factor of the moved windows, continuation launch), then a finalize kernel --
+ * one fixed, data-independent chain on `stream` with no host read-back, so it can be captured; a pass with
+ * nothing to continue exits in every kernel after one load of the pass count.  Results are bit-identical to
+ * passes = 0 whenever P is at least the number of passes the solve needs; an instance still waiting after pass P
+ * reports RQP_STATUS_WINDOW_PASSES.  A pass count that never runs out: the rho index moves by at most one entry
+ * per check and a re-centred window [ri - 2, ri + 2] (clipped to the ladder) is left after >= 3 moves, plus one
+ * pass for an instance that enters the solve outside its window:
+ *     P = 1 + ceil(floor(max_iter / check_interval) / 3)        (55 for the defaults 4000 / 25)
+ * Call after rqp_create or rqp_setup, outside any capture.  Accepted and without effect on handles that are not
+ * windowed (they are capturable as they are).  h == NULL or passes < 0: RQP_ERR_ARG.                        */
+int rqp_set_window_passes(rqp_handle* h, int32_t passes);
 
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);

@@ -302,7 +302,7 @@ int build_matrices(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
         set_kp_image(h, f);
         HIP_TRY(h, rqp_launch_factor(h, f, s));
     }
-    if (h->resident) HIP_TRY(h, rqp_launch_pack_res2(h, a.A, nullptr, s));
+    if (h->resident) HIP_TRY(h, rqp_launch_pack_res2(h, a.A, nullptr, nullptr, s));
     if (h->resident64) HIP_TRY(h, rqp_prepare_res64(h));
     if (h->use_mfma) {
         if (!h->W1img) {
@@ -455,7 +455,7 @@ int rqp_setup(rqp_handle* h, const void* H, const void* g, const void* A, const 
         HIP_TRY(h, hipMalloc((void**)&h->ax_d, B * m * sizeof(double)));
         HIP_TRY(h, hipMalloc((void**)&h->cstat_d, B * sizeof(int32_t)));
         HIP_TRY(h, hipMemsetAsync(h->cstat_d, 0, B * sizeof(int32_t), s));
-        HIP_TRY(h, hipMalloc((void**)&h->ncont_d, sizeof(int32_t)));
+        HIP_TRY(h, hipMalloc((void**)&h->ncont_d, 2 * sizeof(int32_t)));
         HIP_TRY(h, hipHostMalloc((void**)&h->ncont_h, sizeof(int32_t), hipHostMallocDefault));
         HIP_TRY(h, hipMalloc((void**)&h->cont_iter_d, B * sizeof(int32_t)));
         HIP_TRY(h, hipMalloc((void**)&h->cont_rho_d, B * sizeof(double)));
@@ -607,13 +607,15 @@ int rqp_clear_primal_dual(rqp_handle* h, void* stream) {
 
 // Windowed handles: re-centre and re-factor the windows of the marked instances (cstat = 1): k_rewindow -> K_j of the new
 // windows -> their kernel images.  Every kernel filters on cstat, so nothing here needs the host to know which instances.
-static int refactor_windows(rqp_handle* h, int all, hipStream_t s) {
-    HIP_TRY(h, rqp_launch_rewindow(h, all, s));
+// gate (fixed-pass protocol): the pass's pending count -- every kernel returns at once when it is 0.
+static int refactor_windows(rqp_handle* h, int all, const int32_t* gate, hipStream_t s) {
+    HIP_TRY(h, rqp_launch_rewindow(h, all, gate, s));
     SetupArgs f = make_setup_args(h, nullptr, nullptr, nullptr, nullptr, nullptr);
     f.only = h->cstat_d;
+    f.gate = gate;
     set_kp_image(h, f);
     HIP_TRY(h, rqp_launch_factor(h, f, s));
-    if (h->resident) HIP_TRY(h, rqp_launch_pack_res2(h, nullptr, h->cstat_d, s));
+    if (h->resident) HIP_TRY(h, rqp_launch_pack_res2(h, nullptr, h->cstat_d, gate, s));
     return RQP_OK;
 }
 
@@ -633,11 +635,12 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
         a.order = h->order_valid ? h->order_d : nullptr;
         a.last_iter = h->last_iter_d;
     }
+    const bool fixed_passes = h->windowed && h->window_passes > 0;   // rqp_set_window_passes: no host read-back
     if (h->windowed) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        if (!fixed_passes && hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
             return fail_unsupported(h, "rqp_solve: a windowed handle synchronises the stream (rho-ladder window); set up with "
-                                       "RQP_FLAG_FULL_LADDER to capture solves into a HIP graph");
+                                       "RQP_FLAG_FULL_LADDER, or call rqp_set_window_passes, to capture solves into a HIP graph");
         HIP_TRY(h, hipMemsetAsync(h->ncont_d, 0, sizeof(int32_t), s));
     }
     // Infeasibility certificates: the streaming kernel tests them at every check; the register-resident / MFMA kernels
@@ -662,7 +665,27 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
         HIP_TRY(h, rqp_launch_solve_res2(h, c, s));
     }
     const bool ranks = h->order_d && h->last_iter_d && h->use_history;   // rank the instances by what they just needed: next launch goes longest-first
-    if (h->windowed) {
+    if (fixed_passes) {
+        // The same continuation passes as the host loop below, a fixed number of them, each behind a gate kernel that turns the
+        // previous launch's count into the pass's pending count: in a pass with nothing pending every kernel returns after
+        // one load.  One linear chain on `s`, no host read-back (capturable).  The ranking runs once, after the finalize
+        // kernel (the continuation launches issue in grid order; only the next solve's launch reads the order).
+        SolveArgs c = a;
+        c.cont = 2;
+        c.order = nullptr;
+        c.gate = h->ncont_d + 1;
+        for (int p = 0; p < h->window_passes; ++p) {
+            HIP_TRY(h, rqp_launch_window_gate(h, s));
+            const int rc = refactor_windows(h, 0, c.gate, s);
+            if (rc != RQP_OK) return rc;
+            HIP_TRY(h, launch_solve(h, c, s));
+        }
+        HIP_TRY(h, rqp_launch_window_finalize(h, a, s));
+        if (ranks) {
+            HIP_TRY(h, rqp_launch_order_lpt(h, s));
+            h->order_valid = true;
+        }
+    } else if (h->windowed) {
         // instances whose rho index left their window stopped with their exact state: new windows, then they continue
         // (at most one window move per `RQP_WINDOW / 2` index moves, i.e. per >= 2 checks of an instance).  The ranking is
         // enqueued BEFORE the host reads the count (nothing left the window in the common case: the host's wake-up latency
@@ -672,7 +695,7 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
             HIP_TRY(h, hipMemcpyAsync(h->ncont_h, h->ncont_d, sizeof(int32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(h, hipStreamSynchronize(s));
             if (*h->ncont_h <= 0) break;
-            const int rc = refactor_windows(h, 0, s);
+            const int rc = refactor_windows(h, 0, nullptr, s);
             if (rc != RQP_OK) return rc;
             HIP_TRY(h, hipMemsetAsync(h->ncont_d, 0, sizeof(int32_t), s));
             SolveArgs c = a;
@@ -709,7 +732,7 @@ int rqp_iterate(rqp_handle* h, int32_t k, void* stream) {
     a.max_iter = k;
     h->cold_state = false;
     if (h->windowed) {                              // (test hook: no exit-and-continue here -- every window is centred first)
-        const int rc = refactor_windows(h, 1, (hipStream_t)stream);
+        const int rc = refactor_windows(h, 1, nullptr, (hipStream_t)stream);
         if (rc != RQP_OK) return rc;
     }
     HIP_TRY(h, launch_solve(h, a, (hipStream_t)stream));
@@ -794,6 +817,13 @@ int rqp_get_window(rqp_handle* h, int32_t* slots, int32_t* wbase, void* stream) 
         HIP_TRY(h, hipSetDevice(h->device));
         HIP_TRY(h, hipMemcpyAsync(wbase, h->wbase_d, (size_t)h->nmat * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     }
+    return RQP_OK;
+}
+
+int rqp_set_window_passes(rqp_handle* h, int32_t passes) {
+    if (!h) return RQP_ERR_ARG;
+    if (passes < 0) return fail_arg(h, "rqp_set_window_passes: passes < 0");
+    h->window_passes = passes;
     return RQP_OK;
 }
 

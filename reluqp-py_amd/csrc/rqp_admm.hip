@@ -151,6 +151,7 @@ __global__ void __launch_bounds__(RQP_NT) k_admm_generic(SolveArgs a) {
     int k0 = 0;
     bool exact = false;
     if (a.cont == 2) {
+        if (a.gate && *a.gate == 0) return;                        // (uniform) fixed-pass protocol: an idle pass
         if (a.cstat[b] == 0) return;
         const int ci = a.cont_iter[b];
         if (ci >= 0) {

@@ -81,7 +81,9 @@ struct rqp_handle {
     int32_t* wbase_d = nullptr;   // [nmat] ladder index of slot 0
     double* ax_d = nullptr;       // [B][m] A x of an instance that left its window (exact continuation)
     int32_t* cstat_d = nullptr;   // [B] 1: left its window, continue after the re-factor
-    int32_t* ncont_d = nullptr;   // instances that left their window in the last pass
+    int32_t* ncont_d = nullptr;   // [2] instances that left their window in the last pass; [1]: pending count of the current
+                                  // pass of the fixed-pass protocol (k_window_gate)
+    int window_passes = 0;        // rqp_set_window_passes: 0 = host loop, P >= 1 = P gated continuation passes, no host read-back
     int32_t* ncont_h = nullptr;   // (pinned host copy)
     // Dispatch order of the per-instance kernels.  Workgroups are issued in grid order and an instance runs as long as its
     // iteration count, so the launch ends with a tail of late, long solves (14 % of the headline launch, measured).  After
@@ -144,6 +146,7 @@ struct SolveArgs {
     int32_t* ncont;
     int32_t* cont_iter;       // [B] iterations done at the hand-off
     double* cont_rho;         // [B] carried rho estimate at the hand-off (Q4)
+    const int32_t* gate;      // cont = 2 of the fixed-pass protocol: pending count of the pass (0: return at once; NULL: no gate)
     const int32_t* order;     // workgroup -> instance (NULL: identity)
     int32_t* last_iter;       // iteration count of this solve, for the next launch's order (NULL: not recorded)
     double *r_pri, *r_dua, *r_rho, *r_obj;   // mode 2 outputs
@@ -160,6 +163,7 @@ struct SetupArgs {
     int kwin;                 // K slots per matrix; slot s <-> ladder index (wbase ? wbase[mat] : 0) + s
     const int32_t* wbase;
     const int32_t* only;      // [nmat] (NULL: all) build only the matrices with only[mat] != 0 (re-factor of a moved window)
+    const int32_t* gate;      // with `only`: pending count of the fixed-pass protocol (0: nothing moved, return at once; NULL: no gate)
     // k_factor_reg2 writes K_j straight into the register image of k_admm_res2 (rqp_handle.kpack_direct; NULL: row-major table K)
     float* kp_img;            // Kpack[mat][slot][pair][256][2]
     int kp_cw, kp_kr, kp_kc;  // tile constants of the handle's Res2Cfg: columns per wave, K rows per lane, K columns per lane
@@ -186,7 +190,10 @@ hipError_t rqp_launch_unscale_out(const rqp_handle* h, void* x, void* z, void* l
 hipError_t rqp_launch_order_lpt(const rqp_handle* h, hipStream_t s);
 hipError_t rqp_launch_order_by(const rqp_handle* h, const int32_t* key, hipStream_t s);
 hipError_t rqp_launch_get_K(const rqp_handle* h, const void* Kmat, void* out, hipStream_t s);
-hipError_t rqp_launch_rewindow(const rqp_handle* h, int all, hipStream_t s);
+hipError_t rqp_launch_rewindow(const rqp_handle* h, int all, const int32_t* gate, hipStream_t s);
+// fixed-pass window protocol (rqp_set_window_passes): pending count of the next pass, and the exhausted instances' results
+hipError_t rqp_launch_window_gate(const rqp_handle* h, hipStream_t s);
+hipError_t rqp_launch_window_finalize(const rqp_handle* h, const SolveArgs& a, hipStream_t s);
 
 // one-time launch preparation (dynamic-LDS function attributes), called from rqp_setup for the selected kernels
 hipError_t rqp_prepare_generic(const rqp_handle* h);
@@ -198,7 +205,8 @@ size_t rqp_generic_lds_bytes(const rqp_handle* h);
 bool rqp_res2_fits(const rqp_handle* h);
 void rqp_res2_pack_elems(const rqp_handle* h, size_t* a_elems, size_t* k_elems, size_t* h_elems);
 void rqp_res2_kp_layout(const rqp_handle* h, int* cw, int* kr, int* kc);
-hipError_t rqp_launch_pack_res2(const rqp_handle* h, const void* A_src, const int32_t* only, hipStream_t s);   // A_src NULL: Apack is kept
+hipError_t rqp_launch_pack_res2(const rqp_handle* h, const void* A_src, const int32_t* only, const int32_t* gate,
+                                hipStream_t s);   // A_src NULL: Apack is kept
 hipError_t rqp_launch_solve_res2(const rqp_handle* h, const SolveArgs& a, hipStream_t s);
 
 bool rqp_res64_fits(const rqp_handle* h);

@@ -171,6 +171,7 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         }
         k0 = a.cont_iter[b];
     } else if (a.cont == 2) {
+        if (a.gate && *a.gate == 0) return;                        // (uniform) fixed-pass protocol: an idle pass
         if (a.cstat[b] == 0) return;
         const int ci = a.cont_iter[b];
         if (ci >= 0) {
@@ -824,9 +825,10 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
 //   KH: Kpack holds fp16 pairs (one dword per row pair) of K_j / Kscale[mat][j], Kscale = 2^e with max|K_j| / Kscale <= 2^14
 template <class C, bool KH>
 __global__ void k_pack_res2(int n, int ldn, int nrho, const float* __restrict__ K, float* __restrict__ Kpack, float* __restrict__ Kscale,
-                            const int32_t* __restrict__ only) {
+                            const int32_t* __restrict__ only, const int32_t* __restrict__ gate) {
     constexpr int KR = C::KR, KC = C::KC, NT = C::NT, CW = C::CW, KE2 = C::KE2;
     const int mat = blockIdx.y;                                    // (nrho here = K slots per matrix, rqp_handle.kwin)
+    if (gate && *gate == 0) return;                                // fixed-pass protocol: no window moved
     if (only && !only[mat]) return;                                // re-pack of moved windows only
     const int t = threadIdx.x, w = t >> 6, lane = t & 63;
     const int rr = lane >> 3, cc = lane & 7;
@@ -970,26 +972,26 @@ void rqp_res2_kp_layout(const rqp_handle* h, int* cw, int* kr, int* kc) {
 }
 
 template <class C>
-static hipError_t pack_t(const rqp_handle* h, const void* A_src, const int32_t* only, hipStream_t s) {
+static hipError_t pack_t(const rqp_handle* h, const void* A_src, const int32_t* only, const int32_t* gate, hipStream_t s) {
     const size_t stage_ah = (size_t)(C::M / 4 > h->n ? C::M / 4 : h->n) * h->ldn * sizeof(float);
     const size_t stage_k = (size_t)h->n * h->ldn * sizeof(float);
     // only != NULL: the K blocks of the matrices whose window moved (A and H have not changed)
     if (!only)
         k_pack_res2_ah<C><<<dim3(5, h->nmat), C::NT, stage_ah, s>>>(h->n, h->m, h->ldn, (const float*)A_src, (const float*)h->Ht, h->Apack, h->Hpack);
     if (h->dims.tile_dtype == RQP_TILE_F16) {
-        k_pack_res2<C, true><<<dim3(h->kwin, h->nmat), C::NT, stage_k, s>>>(h->n, h->ldn, h->kwin, (const float*)h->K, h->Kpack, h->Kscale, only);
+        k_pack_res2<C, true><<<dim3(h->kwin, h->nmat), C::NT, stage_k, s>>>(h->n, h->ldn, h->kwin, (const float*)h->K, h->Kpack, h->Kscale, only, gate);
     } else {
         if (!h->k_direct && !h->kpack_direct)       // (low-memory handles read K from the row-major table; kpack_direct: the factor kernel wrote the image)
-            k_pack_res2<C, false><<<dim3(h->kwin, h->nmat), C::NT, stage_k, s>>>(h->n, h->ldn, h->kwin, (const float*)h->K, h->Kpack, nullptr, only);
+            k_pack_res2<C, false><<<dim3(h->kwin, h->nmat), C::NT, stage_k, s>>>(h->n, h->ldn, h->kwin, (const float*)h->K, h->Kpack, nullptr, only, gate);
     }
     return hipGetLastError();
 }
-hipError_t rqp_launch_pack_res2(const rqp_handle* h, const void* A_src, const int32_t* only, hipStream_t s) {
+hipError_t rqp_launch_pack_res2(const rqp_handle* h, const void* A_src, const int32_t* only, const int32_t* gate, hipStream_t s) {
     switch (res2_pick(h)) {
-        case 0: return pack_t<Cfg2C4>(h, A_src, only, s);
-        case 1: return pack_t<Cfg2M>(h, A_src, only, s);
-        case 3: return pack_t<Cfg2N>(h, A_src, only, s);
-        default: return pack_t<Cfg2C2>(h, A_src, only, s);
+        case 0: return pack_t<Cfg2C4>(h, A_src, only, gate, s);
+        case 1: return pack_t<Cfg2M>(h, A_src, only, gate, s);
+        case 3: return pack_t<Cfg2N>(h, A_src, only, gate, s);
+        default: return pack_t<Cfg2C2>(h, A_src, only, gate, s);
     }
 }
 

@@ -385,6 +385,7 @@ __global__ void __launch_bounds__(256) k_factor(SetupArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int n = a.n;
     const int mat = blockIdx.x / a.kwin, j = blockIdx.x % a.kwin;        // j: K slot; ladder index = window base + slot
+    if (a.gate && *a.gate == 0) return;                                   // (uniform) fixed-pass protocol: nothing moved
     if (a.only && !a.only[mat]) return;
     double* colb = (double*)smem_raw;            // [n]   column k before the sweep
     double* rowb = colb + n;                     // [n]   scaled pivot row
@@ -445,6 +446,7 @@ __global__ void __launch_bounds__(1024) k_factor_blk(SetupArgs a) {
     double* Pb = Rb + P * FB_N;                  // [P][P + 1]  pivot block, then its inverse
     const int n = a.n;
     const int mat = blockIdx.x / a.kwin, jslot = blockIdx.x % a.kwin;
+    if (a.gate && *a.gate == 0) return;                                   // (uniform) fixed-pass protocol: nothing moved
     if (a.only && !a.only[mat]) return;
     double* M = a.fscratch + (size_t)blockIdx.x * n * n;
     const T* Ht = (const T*)a.Ht + (size_t)mat * n * a.ldn;
@@ -571,6 +573,7 @@ __global__ void __launch_bounds__(256) k_factor_fast(SetupArgs a) {
     constexpr int RS = 256 / CN;                 // row slices
     const int n = a.n;
     const int mat = blockIdx.x / a.kwin, j = blockIdx.x % a.kwin;
+    if (a.gate && *a.gate == 0) return;                                   // (uniform) fixed-pass protocol: nothing moved
     if (a.only && !a.only[mat]) return;
     double* colb = (double*)smem_raw;            // [n] column k before the sweep
     double* rowb = colb + n;                     // [n] scaled pivot row
@@ -651,6 +654,7 @@ __global__ void __launch_bounds__(TG * TG, TG == 16 ? 4 : 8) k_factor_reg2(Setup
     __shared__ __attribute__((aligned(16))) double tb[RT][TG][TG + 1];       // one output pass: RT blocks, closed under transposition
     const int n = a.n;
     const int mat = blockIdx.x / a.kwin, jrho = blockIdx.x % a.kwin;     // jrho: K slot; ladder index = window base + slot
+    if (a.gate && *a.gate == 0) return;                                   // (uniform) fixed-pass protocol: nothing moved
     if (a.only && !a.only[mat]) return;                                   // (uniform) re-factor of moved windows only
     const int tid = threadIdx.x, tx = tid & (TG - 1), ty = tid / TG;
     const T* Ht = (const T*)a.Ht + (size_t)mat * n * a.ldn;
@@ -998,7 +1002,8 @@ hipError_t rqp_launch_get_K(const rqp_handle* h, const void* Kmat, void* out, hi
 // centred on their current index.  all = 1 (before rqp_iterate / rqp_compute_residuals, which run no exit-and-continue
 // protocol): every instance whose index lies outside its window is marked (cstat = 1) and re-centred, the others cleared.
 __global__ void k_rewindow(int B, int nrho, int kwin, int all, const int32_t* __restrict__ rho_ind, int32_t* __restrict__ cstat,
-                           int32_t* __restrict__ wbase) {
+                           int32_t* __restrict__ wbase, const int32_t* __restrict__ gate) {
+    if (gate && *gate == 0) return;                                // fixed-pass protocol: nothing left its window
     for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B; b += gridDim.x * blockDim.x) {
         const int ri = rho_ind[b];
         if (all) cstat[b] = (ri < wbase[b] || ri >= wbase[b] + kwin) ? 1 : 0;
@@ -1006,7 +1011,79 @@ __global__ void k_rewindow(int B, int nrho, int kwin, int all, const int32_t* __
     }
 }
 
-hipError_t rqp_launch_rewindow(const rqp_handle* h, int all, hipStream_t s) {
-    k_rewindow<<<(h->B + 255) / 256, 256, 0, s>>>(h->B, h->nrho, h->kwin, all, h->rho_ind, h->cstat_d, h->wbase_d);
+hipError_t rqp_launch_rewindow(const rqp_handle* h, int all, const int32_t* gate, hipStream_t s) {
+    k_rewindow<<<(h->B + 255) / 256, 256, 0, s>>>(h->B, h->nrho, h->kwin, all, h->rho_ind, h->cstat_d, h->wbase_d, gate);
+    return hipGetLastError();
+}
+
+// Fixed-pass window protocol (rqp_set_window_passes).  Head of every pass: the count of instances the previous launch sent
+// to a re-window becomes the pending count of this pass (ncont[1], read by every kernel of the pass), the accumulator is
+// cleared for the pass's own launch.  One thread: plain stores, the next kernel on the stream sees them.
+__global__ void k_window_gate(int32_t* __restrict__ ncont) {
+    if (threadIdx.x == 0) {
+        ncont[1] = ncont[0];
+        ncont[0] = 0;
+    }
+}
+
+hipError_t rqp_launch_window_gate(const rqp_handle* h, hipStream_t s) {
+    k_window_gate<<<1, 64, 0, s>>>(h->ncont_d);
+    return hipGetLastError();
+}
+
+// After the last pass: an instance still marked (cstat = 1) waited for a re-window the pass budget did not cover.  It reports
+// RQP_STATUS_WINDOW_PASSES with its exact state at the stop (the exiting kernel persisted x, z, lam, rho_ind, the iteration
+// count and the carried estimate; cont_iter < 0: it never started, the incoming state stands), residuals and objective NaN
+// (not evaluated), and leaves what a finished instance leaves: cstat cleared, its state cleared when warm_starting = 0, its
+// iteration count recorded for the dispatch order.  A later solve then continues it like any other instance.  One wavefront
+// per marked instance (ballot over one 256-instance block per workgroup; none marked: one load per thread).
+template <typename T>
+__global__ void __launch_bounds__(256) k_window_finalize(SolveArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int base = blockIdx.x * 256 + (threadIdx.x & ~63);
+    const int bt = base + lane;
+    unsigned long long mask = __ballot(bt < a.B && a.cstat[bt] != 0);
+    const int n = a.n, m = a.m;
+    const double qnan = __builtin_nan("");
+    while (mask) {
+        const int b = base + (__ffsll(mask) - 1);
+        mask &= mask - 1;
+        const int ci = a.cont_iter[b], ri = a.rho_ind[b];
+        const bool clear = !(a.warm_starting || a.keep_state);
+        for (int i = lane; i < n; i += 64) {
+            const size_t o = (size_t)b * n + i;
+            if (a.out_x) ((T*)a.out_x)[o] = (T)a.x[o];
+            if (clear) a.x[o] = 0.0;
+        }
+        for (int i = lane; i < m; i += 64) {
+            const size_t o = (size_t)b * m + i;
+            if (a.out_z) ((T*)a.out_z)[o] = (T)a.z[o];
+            if (a.out_lam) ((T*)a.out_lam)[o] = (T)a.lam[o];
+            if (clear) {
+                a.z[o] = 0.0;
+                a.lam[o] = 0.0;
+            }
+        }
+        if (lane == 0) {
+            a.cstat[b] = 0;
+            if (a.info.iter) a.info.iter[b] = ci > 0 ? ci : 0;
+            if (a.last_iter) a.last_iter[b] = a.max_iter;
+            if (a.info.status) a.info.status[b] = RQP_STATUS_WINDOW_PASSES;
+            if (a.info.rho_ind) a.info.rho_ind[b] = ri;
+            if (a.info.pri_res) a.info.pri_res[b] = qnan;
+            if (a.info.dua_res) a.info.dua_res[b] = qnan;
+            if (a.info.rho_estimate) a.info.rho_estimate[b] = ci >= 0 ? a.cont_rho[b] : a.rhos[ri];
+            if (a.info.obj_val) a.info.obj_val[b] = qnan;
+            if (clear) a.rho_ind[b] = a.rho_ind0;
+        }
+    }
+}
+
+hipError_t rqp_launch_window_finalize(const rqp_handle* h, const SolveArgs& a, hipStream_t s) {
+    const int grid = (h->B + 255) / 256;
+    if (h->esz == 4)
+        k_window_finalize<float><<<grid, 256, 0, s>>>(a);
+    else
+        k_window_finalize<double><<<grid, 256, 0, s>>>(a);
     return hipGetLastError();
 }

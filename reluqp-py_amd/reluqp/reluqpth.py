@@ -35,6 +35,14 @@ _FROZEN = ("rho", "rho_min", "rho_max", "sigma", "adaptive_rho", "adaptive_rho_i
            "adaptive_rho_tolerance")
 
 
+def window_pass_bound(max_iter, check_interval):
+    """``graph_passes`` that never runs out (include/rqp_abi.h, rqp_set_window_passes): the rho index moves by at most one
+    entry per check, a re-centred window is left after >= 3 moves, plus one pass for an instance that enters the solve
+    outside its window.  55 for the defaults (4000, 25)."""
+    checks = int(max_iter) // int(check_interval)
+    return 1 + (checks + 2) // 3
+
+
 class _Layers(object):
     """Stand-in for the reference's ``ReLU_QP.layers`` (class ReLU_Layer, reluqpth.py:8-89):
     exposes the rho ladder and the per-rho KKT inverses; W is never materialised."""
@@ -137,7 +145,8 @@ class ReLU_QP(object):
               iterate_dtype=None,
               devices=None,
               low_memory=False,
-              full_ladder=False):
+              full_ladder=False,
+              graph_passes=None):
         """
         Setup ReLU-QP solver problem of the form
 
@@ -163,8 +172,12 @@ class ReLU_QP(object):
         image -- ~12 % less workspace, 1 % more solve time, bit-identical results.  ``full_ladder=True`` (RQP_FLAG_FULL_LADDER): build
         K(rho) for every entry of the rho ladder of every matrix as the reference does (reluqpth.py:52-78); by default batches
         of >= 32 per-instance matrices keep a window of 5 entries around each instance's index and re-factor on demand
-        (bit-identical results, ~3x less setup time and workspace; solve() then synchronises the stream, so use
-        full_ladder=True under HIP-graph capture).
+        (bit-identical results, ~3x less setup time and workspace; solve() then synchronises the stream after every pass).
+        ``graph_passes=P`` (C-ABI rqp_set_window_passes): a windowed solve() runs P re-window passes whatever happens, with no
+        host synchronisation, so that it can be captured into a HIP graph; bit-identical whenever P covers the passes the
+        solve needs (``window_pass_bound(max_iter, check_interval)`` always does; 2-4 are typical), an instance still waiting
+        after P passes reports status "window_passes_exhausted".  No effect on handles that are not windowed (full_ladder=True,
+        shared H and A, batches below 32): they are capturable as they are.
         """
         if devices is not None:
             from reluqp.multidevice import DeviceShards
@@ -176,7 +189,8 @@ class ReLU_QP(object):
                       adaptive_rho_tolerance=adaptive_rho_tolerance, max_iter=max_iter, eps_abs=eps_abs,
                       check_interval=check_interval, precision=precision, eq_tol=eq_tol, eps_rel=eps_rel,
                       check_infeasibility=check_infeasibility, eps_prim_inf=eps_prim_inf, eps_dual_inf=eps_dual_inf,
-                      kernel=kernel, iterate_dtype=iterate_dtype, low_memory=low_memory, full_ladder=full_ladder)
+                      kernel=kernel, iterate_dtype=iterate_dtype, low_memory=low_memory, full_ladder=full_ladder,
+                      graph_passes=graph_passes)
             self._shards = DeviceShards(ReLU_QP, list(devices), H, g, A, l, u, kw)
             first = self._shards.children[0]
             self.settings, self.QP, self.layers, self._rhos = first.settings, first.QP, first.layers, first._rhos
@@ -224,6 +238,8 @@ class ReLU_QP(object):
             _cabi.check(None, lib.rqp_create(ctypes.byref(h), ctypes.byref(dims), ctypes.byref(cs), device.index),
                         "rqp_create")
             self._h = h
+            if graph_passes is not None:
+                _cabi.check(h, lib.rqp_set_window_passes(h, int(graph_passes)), "rqp_set_window_passes")
             _cabi.check(h, lib.rqp_setup(h, _cabi.ptr(qp.H), _cabi.ptr(qp.g), _cabi.ptr(qp.A), _cabi.ptr(qp.l),
                                          _cabi.ptr(qp.u), self._stream()), "rqp_setup")
             cnt = ctypes.c_int32()
@@ -259,8 +275,9 @@ class ReLU_QP(object):
         qp = self.QP
         lead = (qp.batch,) if qp.batched else ()
         with torch.cuda.device(self.settings.device):
-            start, end = self._events()
-            start.record()
+            if self.synchronous:         # (enqueue only records nothing: update(g, l, u) + solve() can be captured in a graph)
+                start, end = self._events()
+                start.record()
             # The reference asserts here (`updating Hx and Ax is not supported yet`, reluqpth.py:176-177).  SURVEY.md
             # 8(f)-4: Hx / Ax are the new dense H / A (same shapes as at setup); the device re-runs the setup chain
             # (C-ABI rqp_update_mats) and keeps the ADMM state, so the next solve() is warm-started.
@@ -284,8 +301,8 @@ class ReLU_QP(object):
                                                 _cabi.ptr(qp.l if l is not None else None),
                                                 _cabi.ptr(qp.u if u is not None else None), self._stream()),
                         "rqp_update")
-            end.record()
             if self.synchronous:
+                end.record()
                 end.synchronize()
                 self.results.info.update_time = start.elapsed_time(end) / 1000.0
             else:
