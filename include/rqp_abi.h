@@ -291,6 +291,30 @@ int rqp_get_window(rqp_handle* h, int32_t* slots, int32_t* wbase, void* stream);
  * windowed (they are capturable as they are).  h == NULL or passes < 0: RQP_ERR_ARG.                        */
 int rqp_set_window_passes(rqp_handle* h, int32_t passes);
 
+/* OSQP-style solution polishing (OSQP settings polish, delta, polish_refine_iter; defaults 0, 1e-6, 3).  After the ADMM
+ * loop, every instance whose exit is RQP_STATUS_SOLVED guesses its active set from the final iterate (z, lam) in the space
+ * the kernels iterate in -- lower-active: z_i - l_i < -lam_i; upper-active: u_i - z_i < lam_i (rows not lower-active) --
+ * solves the reduced KKT system [[H + delta I, A_a'], [A_a, -delta I]] [x; y_a] = [-g; b_a] (b_i = l_i / u_i), runs
+ * refine_iter steps of iterative refinement against [[H, A_a'], [A_a, 0]], and forms z = clip(A x, l, u) and y = y_a on the
+ * active rows (0 elsewhere) projected onto the sign cone of its row (<= 0 lower, >= 0 upper, free where l_i == u_i).
+ * pri_res, dua_res and obj_val of that point are evaluated in float64 in the caller's units; it is ACCEPTED (status_polish
+ * 1) when both residuals are below the ADMM ones, or one is and the other ADMM residual is already < 1e-10 (OSQP's rule):
+ * x, z, lam and info pri_res, dua_res, obj_val are then replaced.  Otherwise status_polish = -1 and every output is the
+ * ADMM one bit for bit; instances not solved report 0.  iter, status, rho_ind, rho_estimate and the handle's ADMM state
+ * (rqp_get_state, the next warm start) never change.  float64 for every dtype / tile_dtype.
+ * Call before rqp_setup to reserve the workspace (per-instance float64 A' diag(w) A and M^-1, processed in chunks of at
+ * most 1 GiB; a windowed float32 handle then keeps its row-major copy of A).  After setup it switches polish on or off,
+ * and changes delta / refine_iter, only on a handle set up with it (else RQP_ERR_STATE).  delta <= 0 or refine_iter < 0:
+ * RQP_ERR_ARG.  Synchronous; not callable during a stream capture.  A polished solve is as capturable as a plain one; the
+ * captured chain holds enable, delta and refine_iter as they were at capture: recapture after changing them.            */
+int rqp_set_polish(rqp_handle* h, int32_t enable, double delta, int32_t refine_iter);
+
+/* Polish results of the last rqp_solve, copied (asynchronously, on `stream`) into DEVICE arrays; either may be NULL:
+ * status_polish [batch] int32: 1 accepted, -1 rejected, 0 not attempted (instance not solved, or polish switched off);
+ * active [batch][m] int8: -1 lower-active, +1 upper-active, 0 inactive (0 on instances not attempted).
+ * RQP_ERR_STATE on a handle not set up with polish.                                                                      */
+int rqp_get_polish(rqp_handle* h, int32_t* status_polish, int8_t* active, void* stream);
+
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);
 

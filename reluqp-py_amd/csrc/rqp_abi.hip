@@ -39,6 +39,10 @@ int fail_arg(rqp_handle* h, const char* what) {
     if (h) h->err = what;
     return RQP_ERR_ARG;
 }
+int fail_state(rqp_handle* h, const char* what) {
+    if (h) h->err = what;
+    return RQP_ERR_STATE;
+}
 int fail_unsupported(rqp_handle* h, const char* what) {
     if (h) h->err = what;
     return RQP_ERR_UNSUPPORTED;
@@ -94,7 +98,9 @@ void free_ws(rqp_handle* h) {
                      (void**)&h->fscratch, (void**)&h->Apack, (void**)&h->Kpack, (void**)&h->Hpack, (void**)&h->Kscale, (void**)&h->W1img, (void**)&h->queue,
                      (void**)&h->flag_d, (void**)&h->order_d, (void**)&h->last_iter_d, (void**)&h->cont_iter_d, (void**)&h->cont_rho_d,
                      (void**)&h->Dsc, (void**)&h->Esc, (void**)&h->csc, (void**)&h->wbase_d, (void**)&h->ax_d, (void**)&h->cstat_d, (void**)&h->key_d,
-                     (void**)&h->ncont_d};
+                     (void**)&h->ncont_d, (void**)&h->polish_G, (void**)&h->polish_Minv, (void**)&h->polish_rho,
+                     (void**)&h->polish_status, (void**)&h->polish_act, (void**)&h->polish_flag, (void**)&h->polish_st_in,
+                     (void**)&h->polish_res_in};
     // hipFree is one of the calls that invalidate a stream capture in progress (global / thread-local capture modes).  A handle
     // may be destroyed while this thread captures something else (a Python finaliser, an explicit `del`): free under the
     // relaxed mode, which exists for exactly this.
@@ -266,7 +272,8 @@ int select_kernels(rqp_handle* h) {
     h->windowed = !h->dims.shared_mats && h->nmat >= 32 && h->nrho > RQP_WINDOW && !(h->dims.flags & RQP_FLAG_FULL_LADDER) &&
                   !h->st.check_infeasibility && !h->use_mfma;
     if (h->windowed) h->kwin = RQP_WINDOW;
-    h->borrow_A = h->windowed && h->resident && h->st.scaling <= 0 && h->ldn == h->n;     // (rqp_common.h)
+    // (rqp_common.h; not on a handle set up for polishing, which reads the row-major A after every solve)
+    h->borrow_A = h->windowed && h->resident && h->st.scaling <= 0 && h->ldn == h->n && !h->polish_reserved;
     h->kpack_direct = h->windowed && h->resident && !h->k_direct && h->dims.tile_dtype != RQP_TILE_F16;
     if (h->use_mfma) h->kernel_name = h->mfmad ? "mfmad" : (h->mfmal ? "mfmal" : (h->mfma16 ? "mfma16" : "mfma"));
     else if (h->use_wave) h->kernel_name = "wave";
@@ -460,6 +467,28 @@ int rqp_setup(rqp_handle* h, const void* H, const void* g, const void* A, const 
         HIP_TRY(h, hipMalloc((void**)&h->cont_iter_d, B * sizeof(int32_t)));
         HIP_TRY(h, hipMalloc((void**)&h->cont_rho_d, B * sizeof(double)));
     }
+    if (h->polish_reserved) {   // solution polishing (rqp_polish.hip): chunked float64 workspace, per-instance results
+        const size_t lds = rqp_polish_lds_bytes(h);
+        if (lds > 160 * 1024) {
+            free_ws(h);
+            return fail_unsupported(h, "rqp_setup: polish needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
+        }
+        h->polish_chunk = rqp_polish_chunk(h);
+        const size_t pc = h->polish_chunk;
+        HIP_TRY(h, hipMalloc((void**)&h->polish_G, pc * n * n * sizeof(double)));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_Minv, pc * n * h->ldn * sizeof(double)));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_rho, sizeof(double)));
+        const double idel = 1.0 / h->polish_delta;
+        HIP_TRY(h, hipMemcpyAsync(h->polish_rho, &idel, sizeof(double), hipMemcpyHostToDevice, s));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_status, B * sizeof(int32_t)));
+        HIP_TRY(h, hipMemsetAsync(h->polish_status, 0, B * sizeof(int32_t), s));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_act, B * m));
+        HIP_TRY(h, hipMemsetAsync(h->polish_act, 0, B * m, s));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_flag, B * sizeof(int32_t)));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_st_in, B * sizeof(int32_t)));
+        HIP_TRY(h, hipMalloc((void**)&h->polish_res_in, 3 * B * sizeof(double)));
+        HIP_TRY(h, hipStreamSynchronize(s));          // (idel lives on this stack frame)
+    }
     h->handoff_cols = 0;
     if (h->use_mfma && h->resident && (h->B + 15) / 16 <= h->ncu) {   // straggler hand-off (SolveArgs): one tile per CU at most
         HIP_TRY(h, hipMalloc((void**)&h->cont_iter_d, (size_t)h->B * sizeof(int32_t)));
@@ -647,6 +676,12 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
     // keep their loops untouched and a mode-3 pass of the streaming kernel examines the instances that ran out of iterations.
     const bool post_cert = h->st.check_infeasibility && a.info.status && (h->use_mfma || h->use_wave || h->resident || h->resident64);
     if (post_cert) a.keep_state = 1;
+    // Solution polishing reads the final iterate of every instance: with warm_starting = 0 the state is kept through the chain
+    // and cleared after the polish kernels (what the solve kernels would have done at their exit).  (On k_admm_mfmal this turns
+    // off the regrouped two-launch cold solve, whose exact continuation gives the same results: tests/test_polish_gpu.py.)
+    const bool polish = h->polish_reserved && h->polish_on;
+    const bool polish_keep = polish && !h->st.warm_starting;
+    if (polish_keep) a.keep_state = 1;
     const bool handoff = h->use_mfma && h->handoff_cols > 0 && a.info.status != nullptr;
     if (handoff) {
         a.handoff_cols = h->handoff_cols;
@@ -654,12 +689,18 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
         a.cont_rho = h->cont_rho_d;
         a.keep_state = 1;                           // the continue pass clears what warm_starting = 0 asks to clear
     }
+    if (polish) {                                   // (after the choices above, which follow the caller's info): internal buffers for
+        if (!a.info.status) a.info.status = h->polish_st_in;                 // the ADMM results polish needs
+        if (!a.info.pri_res) a.info.pri_res = h->polish_res_in;
+        if (!a.info.dua_res) a.info.dua_res = h->polish_res_in + h->B;
+        if (!a.info.obj_val) a.info.obj_val = h->polish_res_in + 2 * h->B;
+    }
     HIP_TRY(h, launch_solve(h, a, s));
     if (handoff) {                                  // stragglers finish on the per-instance resident kernel
         SolveArgs c = a;
         c.cont = 1;
         c.handoff_cols = 0;
-        c.keep_state = post_cert ? 1 : 0;
+        c.keep_state = (post_cert || polish_keep) ? 1 : 0;
         c.order = nullptr;
         c.last_iter = nullptr;
         HIP_TRY(h, rqp_launch_solve_res2(h, c, s));
@@ -711,8 +752,20 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
         c.mode = 3;
         c.order = nullptr;
         c.last_iter = nullptr;
-        c.keep_state = 0;
+        c.keep_state = polish_keep ? 1 : 0;
         HIP_TRY(h, rqp_launch_solve_generic(h, c, s));
+    }
+    if (polish) {                                   // before the un-scaling: the polished outputs are in the scaled space
+        HIP_TRY(h, rqp_launch_polish(h, a, s));
+    } else if (h->polish_reserved) {                // switched off: "not attempted" for every instance
+        HIP_TRY(h, hipMemsetAsync(h->polish_status, 0, (size_t)h->B * sizeof(int32_t), s));
+        HIP_TRY(h, hipMemsetAsync(h->polish_act, 0, (size_t)h->B * h->m, s));
+    }
+    if (polish_keep) {                              // clear_primal_dual (reluqpth.py:324-333), as the kernels do with keep_state = 0
+        HIP_TRY(h, hipMemsetAsync(h->x, 0, (size_t)h->B * h->n * sizeof(double), s));
+        HIP_TRY(h, hipMemsetAsync(h->z, 0, (size_t)h->B * h->m * sizeof(double), s));
+        HIP_TRY(h, hipMemsetAsync(h->lam, 0, (size_t)h->B * h->m * sizeof(double), s));
+        HIP_TRY(h, rqp_launch_state_set(h, nullptr, nullptr, nullptr, 1, h->rho_ind0, s));
     }
     if (ranks && !h->windowed) {
         HIP_TRY(h, rqp_launch_order_lpt(h, s));
@@ -824,6 +877,39 @@ int rqp_set_window_passes(rqp_handle* h, int32_t passes) {
     if (!h) return RQP_ERR_ARG;
     if (passes < 0) return fail_arg(h, "rqp_set_window_passes: passes < 0");
     h->window_passes = passes;
+    return RQP_OK;
+}
+
+int rqp_set_polish(rqp_handle* h, int32_t enable, double delta, int32_t refine_iter) {
+    if (!h) return RQP_ERR_ARG;
+    if (!(delta > 0) || refine_iter < 0) return fail_arg(h, "rqp_set_polish: delta <= 0 or refine_iter < 0");
+    if (!h->is_setup) {                             // before rqp_setup: reserve (or not) the workspace
+        h->polish_reserved = h->polish_on = enable != 0;
+        h->polish_delta = delta;
+        h->polish_refine = refine_iter;
+        return RQP_OK;
+    }
+    if (!h->polish_reserved)
+        return fail_state(h, "rqp_set_polish: the handle was set up without polish (call rqp_set_polish before rqp_setup)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    if (delta != h->polish_delta) {
+        const double idel = 1.0 / delta;
+        HIP_TRY(h, hipMemcpy(h->polish_rho, &idel, sizeof(double), hipMemcpyHostToDevice));
+    }
+    h->polish_on = enable != 0;
+    h->polish_delta = delta;
+    h->polish_refine = refine_iter;
+    return RQP_OK;
+}
+
+int rqp_get_polish(rqp_handle* h, int32_t* status_polish, int8_t* active, void* stream) {
+    if (!h) return RQP_ERR_ARG;
+    if (!h->is_setup || !h->polish_reserved) return fail_state(h, "rqp_get_polish: the handle was not set up with polish");
+    HIP_TRY(h, hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (status_polish)
+        HIP_TRY(h, hipMemcpyAsync(status_polish, h->polish_status, (size_t)h->B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (active) HIP_TRY(h, hipMemcpyAsync(active, h->polish_act, (size_t)h->B * h->m, hipMemcpyDeviceToDevice, s));
     return RQP_OK;
 }
 

@@ -101,6 +101,22 @@ struct rqp_handle {
     int debug = 0;                // bit 0: RQP_DEBUG (occupancy print at setup), bit 1: RQP_DIAG (s_memtime build); read ONCE
                                   // at rqp_create -- diagnostics only, kernel selection never depends on the environment
 
+    // Solution polishing (rqp_set_polish, rqp_polish.hip): reserved at setup (polish_reserved), switched per solve (polish_on).
+    // Workspace: per-instance float64 G_a = A' diag(w) A and M^-1 for polish_chunk instances at a time (2 n^2 doubles each,
+    // capped at RQP_POLISH_WS_BYTES); results of the last solve in polish_status [B] and polish_act [B][m].
+    bool polish_reserved = false, polish_on = false;
+    double polish_delta = 1e-6;
+    int polish_refine = 3;
+    int polish_chunk = 0;         // instances per chunk (fixed at setup: the chain of a solve is data-independent)
+    double* polish_G = nullptr;   // [polish_chunk][n][n]  G_a, then the factor's global scratch when n needs one
+    double* polish_Minv = nullptr;   // [polish_chunk][n][n]  (H + delta I + G_a / delta)^-1
+    double* polish_rho = nullptr;    // [1] 1 / delta (the factor kernels read rho from the ladder array)
+    int32_t* polish_status = nullptr;   // [B] 1 accepted, -1 rejected, 0 not attempted
+    int8_t* polish_act = nullptr;       // [B][m] -1 lower-active, +1 upper-active, 0 inactive
+    int32_t* polish_flag = nullptr;     // [B] 1: polish this instance (its ADMM exit is RQP_STATUS_SOLVED)
+    int32_t* polish_st_in = nullptr;    // [B] ADMM status when the caller passes no info.status
+    double* polish_res_in = nullptr;    // [3][B] ADMM pri_res, dua_res, obj_val when the caller passes none
+
     const char* kernel_name = "generic";
     std::string err;
 };
@@ -167,6 +183,10 @@ struct SetupArgs {
     // k_factor_reg2 writes K_j straight into the register image of k_admm_res2 (rqp_handle.kpack_direct; NULL: row-major table K)
     float* kp_img;            // Kpack[mat][slot][pair][256][2]
     int kp_cw, kp_kr, kp_kc;  // tile constants of the handle's Res2Cfg: columns per wave, K rows per lane, K columns per lane
+    // solution polishing (rqp_polish.hip); all zero on the setup path
+    int mats_shared;          // 1: Ht (factor) and A (masked gram) are one shared matrix, indexed by 0 for every `mat`
+    int k_f64;                // 1: the factor kernels write K in float64 whatever the handle's dtype
+    const int8_t* pw_act;     // masked gram (rqp_launch_gram_masked): row weight w_i = (pw_act[mat][i] != 0)
 };
 
 // launchers (defined in the .hip files); return hipError_t of the launch
@@ -177,6 +197,8 @@ hipError_t rqp_launch_affine_update(const rqp_handle* h, const void* p, int np, 
                                     const void* l0, const void* u0, hipStream_t s);
 hipError_t rqp_launch_vec_update(const rqp_handle* h, const void* g, const void* l, const void* u, hipStream_t s);
 hipError_t rqp_launch_gram(const rqp_handle* h, const SetupArgs& a, hipStream_t s);
+// G[mat] = A[mats_shared ? 0 : mat]' diag(w[mat]) A[...], w from a.pw_act, matrices with a.only[mat] == 0 skipped (polish)
+hipError_t rqp_launch_gram_masked(const rqp_handle* h, const SetupArgs& a, hipStream_t s);
 hipError_t rqp_launch_factor(rqp_handle* h, const SetupArgs& a, hipStream_t s);
 hipError_t rqp_launch_solve_generic(const rqp_handle* h, const SolveArgs& a, hipStream_t s);
 hipError_t rqp_launch_state_set(const rqp_handle* h, const void* x, const void* z, const void* lam, int set_rho,
@@ -194,6 +216,13 @@ hipError_t rqp_launch_rewindow(const rqp_handle* h, int all, const int32_t* gate
 // fixed-pass window protocol (rqp_set_window_passes): pending count of the next pass, and the exhausted instances' results
 hipError_t rqp_launch_window_gate(const rqp_handle* h, hipStream_t s);
 hipError_t rqp_launch_window_finalize(const rqp_handle* h, const SolveArgs& a, hipStream_t s);
+
+// solution polishing (rqp_polish.hip): workspace sizing at setup, and the chain that runs after a solve's kernels (before the
+// un-scaling of the outputs).  `a` carries the solve's outputs and info (status, pri_res, dua_res, obj_val non-NULL).
+#define RQP_POLISH_WS_BYTES ((size_t)1 << 30)
+int rqp_polish_chunk(const rqp_handle* h);
+size_t rqp_polish_lds_bytes(const rqp_handle* h);
+hipError_t rqp_launch_polish(rqp_handle* h, const SolveArgs& a, hipStream_t s);
 
 // one-time launch preparation (dynamic-LDS function attributes), called from rqp_setup for the selected kernels
 hipError_t rqp_prepare_generic(const rqp_handle* h);

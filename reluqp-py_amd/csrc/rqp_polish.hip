@@ -1,0 +1,320 @@
+// rqp_polish.hip -- OSQP-style solution polishing of a batched solve (rqp_set_polish).
+//
+// Per instance whose ADMM exit is RQP_STATUS_SOLVED: guess the active set from the final iterate (z, lam), solve the reduced
+// KKT system of that guess
+//     [[H + delta I, A_a'], [A_a, -delta I]] [x; y_a] = [-g; b_a]
+// with y_a eliminated (y_a = (A_a x - b_a) / delta), i.e. the n x n SPD system
+//     M x = -g + A_a' b_a / delta,   M = H + delta I + (1 / delta) A' diag(w) A,
+// refine it against the unregularised system [[H, A_a'], [A_a, 0]], and keep the result only if its residuals beat the
+// ADMM ones (OSQP's rule).  M is sym(H) + sigma I + rho G with sigma = delta, rho = 1 / delta, G = A' diag(w) A: the setup
+// path's masked gram (rqp_launch_gram_masked) and its factor kernels (rqp_launch_factor, float64 output) build M^-1.
+// Everything is float64 whatever the handle's dtype; the packed (H, A, g, l, u) are read in their own type.  The chain is
+// data-independent (fixed chunk count, every kernel gated on the per-instance flag), so a polished solve stays capturable.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "rqp_common.h"
+
+namespace {
+
+constexpr int PT = 256;   // threads per workgroup of the polish kernels (4 wavefronts)
+
+struct PolishArgs {
+    int n, m, ldn, B, b0, refine, shared;
+    double delta;
+    const void *Ht, *A, *g, *l, *u;          // the handle's packed copies (scaled space when settings.scaling > 0)
+    const int8_t* act;                       // [B][m]
+    const int32_t* flag;                     // [B]
+    const double* Minv;                      // [chunk][n][ldn], instance b0 + blockIdx.x
+    const double *scD, *scE, *scC;           // Ruiz factors (NULL: no scaling)
+    void *out_x, *out_z, *out_lam;           // caller outputs (NULL: not requested); scaled space, un-scaled afterwards
+    double *pri, *dua, *obj;                 // in: the ADMM values; out: the polished ones when accepted
+    int32_t* spol;                           // [B] status_polish
+};
+
+// ---------------------------------------------------------------------------------------------------------------- classify
+// Active set of the final ADMM iterate, in the space the kernels iterate in (OSQP polish.c form_Ared):
+//   lower-active: z - l < -lam;  upper-active (not lower): u - z < lam;  inactive otherwise.
+template <typename T>
+__global__ void __launch_bounds__(PT) k_polish_classify(int B, int m, const int32_t* __restrict__ status,
+                                                        const double* __restrict__ z, const double* __restrict__ lam,
+                                                        const T* __restrict__ l, const T* __restrict__ u,
+                                                        int8_t* __restrict__ act, int32_t* __restrict__ flag,
+                                                        int32_t* __restrict__ spol) {
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bool solved = status[b] == RQP_STATUS_SOLVED;
+    if (tid == 0) {
+        flag[b] = solved ? 1 : 0;
+        spol[b] = 0;                                                  // "not attempted" until k_polish decides
+    }
+    const size_t o = (size_t)b * m;
+    if (!solved) {
+        for (int i = tid; i < m; i += PT) act[o + i] = 0;
+        return;
+    }
+    for (int i = tid; i < m; i += PT) {
+        const double zi = z[o + i], yi = lam[o + i];
+        const double li = (double)l[o + i], ui = (double)u[o + i];
+        int8_t a = 0;
+        if (zi - li < -yi) a = -1;
+        else if (ui - zi < yi) a = 1;
+        act[o + i] = a;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ products (float64)
+// out[c] = sum_r Mat[r][c] w[r] (c < C): a column-oriented product, coalesced over c.  The rows are split over S = 256 / CW
+// thread groups when C is small; the partial sums are added in a fixed order (deterministic).  `part`: LDS [PT] doubles.
+// CW need not divide PT (128 < C <= 192: CW = 192, S = 1): the threads past S * CW hold no column and stay idle.
+template <typename MT>
+__device__ void pcolmv(const MT* __restrict__ Mat, int ld, int R, int C, const double* w, double* out, double* part) {
+    const int tid = threadIdx.x;
+    const int CW = C >= PT ? PT : ((C + 63) / 64) * 64, S = PT / CW;
+    const int c0 = tid % CW, sl = tid / CW;
+    const bool owner = sl < S;
+    for (int cb = 0; cb < C; cb += CW) {
+        const int c = cb + c0;
+        double acc = 0.0;
+        if (owner && c < C) {
+#pragma unroll 4
+            for (int r = sl; r < R; r += S) acc = fma((double)Mat[(size_t)r * ld + c], w[r], acc);
+        }
+        if (S > 1) {                                                   // (S > 1: CW divides PT, every thread owns a column)
+            part[tid] = acc;
+            __syncthreads();
+            if (sl == 0 && c < C) {
+                double t = part[c0];
+                for (int q = 1; q < S; ++q) t += part[q * CW + c0];
+                out[c] = t;
+            }
+            __syncthreads();
+        } else if (owner && c < C) {
+            out[c] = acc;
+        }
+    }
+    __syncthreads();
+}
+
+// out[i] = sum_c A[i][c] x[c] (i < R): one wavefront per row, lanes over the columns, butterfly sum
+template <typename MT>
+__device__ void prowmv(const MT* __restrict__ Mat, int ld, int R, int C, const double* x, double* out) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = wave; i < R; i += PT / 64) {
+        const MT* row = Mat + (size_t)i * ld;
+        double acc = 0.0;
+        for (int c = lane; c < C; c += 64) acc = fma((double)row[c], x[c], acc);
+        for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
+        if (lane == 0) out[i] = acc;
+    }
+    __syncthreads();
+}
+
+// max with NaN propagation (torch.max / the ADMM checks report NaN)
+__device__ __forceinline__ double nmax(double a, double b) { return (a != a) ? a : ((b != b) ? b : fmax(a, b)); }
+
+template <bool SUM>
+__device__ double block_reduce(double v, double* red) {
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double o = __shfl_xor(v, off, 64);
+        v = SUM ? v + o : nmax(v, o);
+    }
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double r = SUM ? ((red[0] + red[1]) + red[2]) + red[3] : nmax(nmax(red[0], red[1]), nmax(red[2], red[3]));
+    __syncthreads();
+    return r;
+}
+
+// ------------------------------------------------------------------------------------ refine, evaluate, accept, write
+// One workgroup per instance of the chunk.  LDS: x, v, t1, t2 [n]; y, r2, ax, bv [m]; part [PT]; red [8] (doubles).
+template <typename T>
+__global__ void __launch_bounds__(PT) k_polish(PolishArgs p) {
+    extern __shared__ __attribute__((aligned(16))) double psm[];
+    const int b = p.b0 + blockIdx.x;
+    if (b >= p.B) return;
+    if (!p.flag[b]) return;                                            // (uniform) not solved: outputs stay the ADMM ones
+    const int n = p.n, m = p.m, ldn = p.ldn, tid = threadIdx.x;
+    double* x = psm;
+    double* v = x + n;
+    double* t1 = v + n;
+    double* t2 = t1 + n;
+    double* y = t2 + n;
+    double* r2 = y + m;
+    double* ax = r2 + m;
+    double* bv = ax + m;
+    double* part = bv + m;
+    double* red = part + PT;
+    const size_t mat = p.shared ? 0 : (size_t)b;
+    const T* Ht = (const T*)p.Ht + mat * n * ldn;
+    const T* A = (const T*)p.A + mat * m * ldn;
+    const T* g = (const T*)p.g + (size_t)b * n;
+    const T* l = (const T*)p.l + (size_t)b * m;
+    const T* u = (const T*)p.u + (size_t)b * m;
+    const int8_t* act = p.act + (size_t)b * m;
+    const double* Mi = p.Minv + (size_t)blockIdx.x * n * ldn;
+    const double idel = 1.0 / p.delta;
+
+    // x = M^-1 (-g + A_a' b_a / delta),  y_a = (A_a x - b_a) / delta
+    for (int i = tid; i < m; i += PT) {
+        const int a = act[i];
+        const double bi = a < 0 ? (double)l[i] : (a > 0 ? (double)u[i] : 0.0);
+        bv[i] = bi;
+        r2[i] = a ? bi * idel : 0.0;
+    }
+    __syncthreads();
+    pcolmv<T>(A, ldn, m, n, r2, t1, part);
+    for (int c = tid; c < n; c += PT) v[c] = t1[c] - (double)g[c];
+    __syncthreads();
+    pcolmv<double>(Mi, ldn, n, n, v, x, part);
+    prowmv<T>(A, ldn, m, n, x, ax);
+    for (int i = tid; i < m; i += PT) y[i] = act[i] ? (ax[i] - bv[i]) * idel : 0.0;
+    __syncthreads();
+
+    // iterative refinement against [[H, A_a'], [A_a, 0]]: residual (r1, r2), correction M dx = r1 + A_a' r2 / delta,
+    // dy = (A_a dx - r2) / delta
+    for (int k = 0; k < p.refine; ++k) {
+        pcolmv<T>(Ht, ldn, n, n, x, t1, part);                         // H x
+        for (int i = tid; i < m; i += PT) {
+            const bool a = act[i] != 0;
+            const double ri = a ? bv[i] - ax[i] : 0.0;
+            r2[i] = ri;
+            ax[i] = a ? y[i] - ri * idel : 0.0;                        // (ax is recomputed below)
+        }
+        __syncthreads();
+        pcolmv<T>(A, ldn, m, n, ax, t2, part);                         // A_a' (y - r2 / delta)
+        for (int c = tid; c < n; c += PT) v[c] = -(double)g[c] - t1[c] - t2[c];   // r1 + A_a' r2 / delta
+        __syncthreads();
+        pcolmv<double>(Mi, ldn, n, n, v, t1, part);                    // dx
+        for (int c = tid; c < n; c += PT) x[c] += t1[c];
+        __syncthreads();
+        prowmv<T>(A, ldn, m, n, t1, ax);                               // A dx
+        for (int i = tid; i < m; i += PT) y[i] = act[i] ? y[i] + (ax[i] - r2[i]) * idel : 0.0;
+        __syncthreads();
+        prowmv<T>(A, ldn, m, n, x, ax);                                // A x
+    }
+
+    // polished point: z = clip(A x, l, u); y projected onto the sign cone of its row (free on equality rows)
+    pcolmv<T>(Ht, ldn, n, n, x, t1, part);                             // H x
+    for (int i = tid; i < m; i += PT) {
+        const int a = act[i];
+        const double li = (double)l[i], ui = (double)u[i];
+        r2[i] = fmin(fmax(ax[i], li), ui);
+        double yi = a ? y[i] : 0.0;
+        if (li != ui) {
+            if (a < 0) yi = fmin(yi, 0.0);
+            else if (a > 0) yi = fmax(yi, 0.0);
+        }
+        y[i] = yi;
+    }
+    __syncthreads();
+    pcolmv<T>(A, ldn, m, n, y, t2, part);                              // A' y
+    // residuals in the caller's units (the ADMM checks' definition: row i of the primal side / E_i, column j of the dual
+    // side / (c D_j)), objective in the scaled space (rqp_launch_unscale_out divides by c)
+    const double* sE = p.scE ? p.scE + mat * m : nullptr;
+    const double* sD = p.scD ? p.scD + mat * n : nullptr;
+    const double sc = p.scC ? p.scC[mat] : 1.0;
+    double vp = 0.0, vd = 0.0, vo = 0.0;
+    for (int i = tid; i < m; i += PT) {
+        double r = fabs(ax[i] - r2[i]);
+        if (sE) r /= sE[i];
+        vp = nmax(vp, r);
+    }
+    for (int c = tid; c < n; c += PT) {
+        const double gc = (double)g[c];
+        double r = fabs(t1[c] + t2[c] + gc);
+        if (sD) r /= sc * sD[c];
+        vd = nmax(vd, r);
+        vo += x[c] * (0.5 * t1[c] + gc);
+    }
+    const double pp = block_reduce<false>(vp, red);
+    const double dp = block_reduce<false>(vd, red);
+    const double op = block_reduce<true>(vo, red);
+    const double pa = p.pri[b], da = p.dua[b];
+    // OSQP's acceptance rule (polish.c)
+    const bool ok = (pp < pa && dp < da) || (pp < pa && da < 1e-10) || (dp < da && pa < 1e-10);
+    if (tid == 0) {
+        p.spol[b] = ok ? 1 : -1;
+        if (ok) {
+            p.pri[b] = pp;
+            p.dua[b] = dp;
+            p.obj[b] = op;
+        }
+    }
+    if (!ok) return;
+    if (p.out_x) for (int c = tid; c < n; c += PT) ((T*)p.out_x)[(size_t)b * n + c] = (T)x[c];
+    if (p.out_z) for (int i = tid; i < m; i += PT) ((T*)p.out_z)[(size_t)b * m + i] = (T)r2[i];
+    if (p.out_lam) for (int i = tid; i < m; i += PT) ((T*)p.out_lam)[(size_t)b * m + i] = (T)y[i];
+}
+
+}  // namespace
+
+int rqp_polish_chunk(const rqp_handle* h) {
+    const size_t per = ((size_t)h->n * h->n + (size_t)h->n * h->ldn) * sizeof(double);   // G_a + M^-1
+    size_t c = RQP_POLISH_WS_BYTES / per;
+    if (c < 1) c = 1;
+    if (c > (size_t)h->B) c = h->B;
+    return (int)c;
+}
+
+size_t rqp_polish_lds_bytes(const rqp_handle* h) { return (4 * (size_t)h->n + 4 * (size_t)h->m + PT + 8) * sizeof(double); }
+
+hipError_t rqp_launch_polish(rqp_handle* h, const SolveArgs& a, hipStream_t s) {
+    const bool f32 = h->esz == 4;
+    const size_t lds = rqp_polish_lds_bytes(h);
+    hipError_t e = f32 ? rqp_raise_lds_limit((const void*)k_polish<float>, lds) : rqp_raise_lds_limit((const void*)k_polish<double>, lds);
+    if (e != hipSuccess) return e;
+    if (f32)
+        k_polish_classify<float><<<h->B, PT, 0, s>>>(h->B, h->m, a.info.status, h->z, h->lam, (const float*)h->l, (const float*)h->u,
+                                                     h->polish_act, h->polish_flag, h->polish_status);
+    else
+        k_polish_classify<double><<<h->B, PT, 0, s>>>(h->B, h->m, a.info.status, h->z, h->lam, (const double*)h->l, (const double*)h->u,
+                                                      h->polish_act, h->polish_flag, h->polish_status);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const bool sh = h->dims.shared_mats != 0;
+    const size_t esz = h->esz;
+    PolishArgs p;
+    p.n = h->n; p.m = h->m; p.ldn = h->ldn; p.B = h->B; p.refine = h->polish_refine; p.shared = sh ? 1 : 0;
+    p.delta = h->polish_delta;
+    p.Ht = h->Ht; p.A = h->A; p.g = h->g; p.l = h->l; p.u = h->u;
+    p.act = h->polish_act; p.flag = h->polish_flag; p.Minv = h->polish_Minv;
+    p.scD = h->st.scaling > 0 ? h->Dsc : nullptr;
+    p.scE = h->st.scaling > 0 ? h->Esc : nullptr;
+    p.scC = h->st.scaling > 0 ? h->csc : nullptr;
+    p.out_x = a.out_x; p.out_z = a.out_z; p.out_lam = a.out_lam;
+    p.pri = a.info.pri_res; p.dua = a.info.dua_res; p.obj = a.info.obj_val;
+    p.spol = h->polish_status;
+    const int chunk = h->polish_chunk;
+    for (int b0 = 0; b0 < h->B; b0 += chunk) {
+        const int cb = std::min(chunk, h->B - b0);
+        SetupArgs f;
+        memset(&f, 0, sizeof(f));
+        f.n = h->n; f.m = h->m; f.ldn = h->ldn; f.ldm = h->ldm; f.nrho = 1; f.B = h->B; f.nmat = cb;
+        f.sigma = h->polish_delta;
+        f.Ht = (char*)h->Ht + (sh ? 0 : (size_t)b0 * h->n * h->ldn * esz);
+        f.A = (char*)h->A + (sh ? 0 : (size_t)b0 * h->m * h->ldn * esz);
+        f.G = h->polish_G;
+        f.K = h->polish_Minv;
+        f.rhos = h->polish_rho;
+        // The factor kernels that work in a global scratch slab (n > 142) read G[i] and then write the slab's element i in the same
+        // thread: the slab can be G_a itself (1 workgroup per matrix, kwin = 1).
+        f.fscratch = h->polish_G;
+        f.kwin = 1;
+        f.only = h->polish_flag + b0;
+        f.mats_shared = sh ? 1 : 0;
+        f.k_f64 = 1;
+        f.pw_act = h->polish_act + (size_t)b0 * h->m;
+        e = rqp_launch_gram_masked(h, f, s);
+        if (e != hipSuccess) return e;
+        e = rqp_launch_factor(h, f, s);
+        if (e != hipSuccess) return e;
+        p.b0 = b0;
+        if (f32) k_polish<float><<<cb, PT, lds, s>>>(p);
+        else k_polish<double><<<cb, PT, lds, s>>>(p);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}

@@ -159,7 +159,8 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
     bool exact = false;                                            // resume behind the check of iteration k0 with A x = ax
     if (a.cont == 1) {
         if (a.info.status[b] != RQP_STATUS_CONTINUE) {             // (uniform per workgroup)
-            if (!a.warm_starting) {                                // the first kernel kept every state for this pass: clear it
+            if (!(a.warm_starting || a.keep_state)) {              // the first kernel kept every state for this pass: clear it
+                                                                   // (unless a later pass needs it: certificates, polish)
                 for (int i = tid; i < n; i += NT) a.x[(size_t)b * n + i] = 0.0;
                 for (int i = tid; i < m; i += NT) {
                     a.z[(size_t)b * m + i] = 0.0;

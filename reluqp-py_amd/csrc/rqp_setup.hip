@@ -215,14 +215,20 @@ hipError_t rqp_launch_affine_update(const rqp_handle* h, const void* p, int np, 
 // one matrix; 16x16 threads, 4x4 register tile each; A staged through LDS 16 rows at a time.
 #define GR_T 64
 #define GR_K 16
-template <typename T>
+// PW (solution polishing): the row weights are w_i = (pw_act[mat][i] != 0), A is indexed by 0 when a.mats_shared, and the
+// matrices with only[mat] == 0 are skipped.
+template <typename T, bool PW = false>
 __global__ void __launch_bounds__(256) k_gram(SetupArgs a) {
     __shared__ double sR[GR_K][GR_T + 1];
     __shared__ double sC[GR_K][GR_T + 1];
     const int mat = blockIdx.z;
+    if constexpr (PW) {
+        if (a.only && !a.only[mat]) return;                                // (uniform)
+    }
     const int r0 = blockIdx.y * GR_T, c0 = blockIdx.x * GR_T;
-    const T* A = (const T*)a.A + (size_t)mat * a.m * a.ldn;
+    const T* A = (const T*)a.A + (size_t)((PW && a.mats_shared) ? 0 : mat) * a.m * a.ldn;
     const T* cv = (const T*)a.c + (size_t)mat * a.m;   // shared mats: instance 0's pattern (mat = 0)
+    const int8_t* act = PW ? a.pw_act + (size_t)mat * a.m : nullptr;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
     double acc[4][4];
 #pragma unroll
@@ -235,7 +241,8 @@ __global__ void __launch_bounds__(256) k_gram(SetupArgs a) {
             int k = k0 + kk;
             double vr = 0.0, vc = 0.0;
             if (k < a.m) {
-                if (r0 + cc < a.n) vr = (double)A[(size_t)k * a.ldn + r0 + cc] * (double)cv[k];
+                const double ck = PW ? (act[k] != 0 ? 1.0 : 0.0) : (double)cv[k];
+                if (r0 + cc < a.n) vr = (double)A[(size_t)k * a.ldn + r0 + cc] * ck;
                 if (c0 + cc < a.n) vc = (double)A[(size_t)k * a.ldn + c0 + cc];
             }
             sR[kk][cc] = vr;
@@ -280,12 +287,13 @@ typedef double gm_d4 __attribute__((ext_vector_type(4)));
 constexpr int gm_tile_I(int g, int RT) { int I = 0; while (g >= RT - I) { g -= RT - I; ++I; } return I; }
 constexpr int gm_tile_J(int g, int RT) { int I = 0; while (g >= RT - I) { g -= RT - I; ++I; } return I + g; }
 
-template <typename T, int RT, int W>
+template <typename T, int RT, int W, bool PW = false>
 __device__ __forceinline__ void gram_mfma_wave(const SetupArgs& a, int mat, int lane) {
     constexpr int NTILE = RT * (RT + 1) / 2, TPW = (NTILE - W + 3) / 4, KU = (sizeof(T) == 4) ? 2 : 4;
     const int n = a.n, m = a.m, ldn = a.ldn, i16 = lane & 15, kq = lane >> 4;
-    const T* A = (const T*)a.A + (size_t)mat * m * ldn;
+    const T* A = (const T*)a.A + (size_t)((PW && a.mats_shared) ? 0 : mat) * m * ldn;   // (PW: polish, k_gram)
     const T* cv = (const T*)a.c + (size_t)mat * m;                       // shared mats: instance 0's pattern (mat = 0)
+    const int8_t* act = PW ? a.pw_act + (size_t)mat * m : nullptr;
     gm_d4 acc[TPW > 0 ? TPW : 1];
 #pragma unroll
     for (int e = 0; e < TPW; ++e) acc[e] = (gm_d4){0.0, 0.0, 0.0, 0.0};
@@ -299,7 +307,9 @@ __device__ __forceinline__ void gram_mfma_wave(const SetupArgs& a, int mat, int 
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
             const int k = k0 + 4 * u + kq, kc = min(k, m - 1);
-            const T cl = cv[kc];
+            T cl;
+            if constexpr (PW) cl = act[kc] != 0 ? T(1) : T(0);
+            else cl = cv[kc];
             c[u] = (k < m) ? cl : T(0);
             const T* Ar = A + (size_t)kc * ldn;
 #pragma unroll
@@ -352,6 +362,19 @@ __global__ void __launch_bounds__(256, (sizeof(T) == 4) ? 3 : 2) k_gram_mfma(Set
     }
 }
 
+// Masked variant (solution polishing, rqp_polish.hip): G_a = A' diag(w) A with w from the per-instance active set
+template <typename T, int RT>
+__global__ void __launch_bounds__(256, (sizeof(T) == 4) ? 3 : 2) k_gram_mfma_masked(SetupArgs a) {
+    const int mat = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (a.only && !a.only[mat]) return;                                   // (uniform) instance not polished
+    switch (__builtin_amdgcn_readfirstlane(wave)) {
+        case 0: gram_mfma_wave<T, RT, 0, true>(a, mat, lane); break;
+        case 1: gram_mfma_wave<T, RT, 1, true>(a, mat, lane); break;
+        case 2: gram_mfma_wave<T, RT, 2, true>(a, mat, lane); break;
+        default: gram_mfma_wave<T, RT, 3, true>(a, mat, lane); break;
+    }
+}
+
 hipError_t rqp_launch_gram(const rqp_handle* h, const SetupArgs& a, hipStream_t s) {
     // n <= 112: the float64 MFMA kernel (upper 16 x 16 tiles only, like k_factor_reg2 reads them)
     if (h->n <= 32) {
@@ -376,11 +399,35 @@ hipError_t rqp_launch_gram(const rqp_handle* h, const SetupArgs& a, hipStream_t 
     return hipGetLastError();
 }
 
+// Same size predicates as rqp_launch_gram; a.nmat matrices (a chunk of the batch)
+hipError_t rqp_launch_gram_masked(const rqp_handle* h, const SetupArgs& a, hipStream_t s) {
+    const int nm = a.nmat;
+    if (h->n <= 32) {
+        if (h->esz == 4) k_gram_mfma_masked<float, 2><<<nm, 256, 0, s>>>(a); else k_gram_mfma_masked<double, 2><<<nm, 256, 0, s>>>(a);
+        return hipGetLastError();
+    }
+    if (h->n <= 64) {
+        if (h->esz == 4) k_gram_mfma_masked<float, 4><<<nm, 256, 0, s>>>(a); else k_gram_mfma_masked<double, 4><<<nm, 256, 0, s>>>(a);
+        return hipGetLastError();
+    }
+    if (h->n <= 112 && h->ldn <= 112) {
+        if (h->esz == 4) k_gram_mfma_masked<float, 7><<<nm, 256, 0, s>>>(a); else k_gram_mfma_masked<double, 7><<<nm, 256, 0, s>>>(a);
+        return hipGetLastError();
+    }
+    int t = (h->n + GR_T - 1) / GR_T;
+    dim3 grid(t, t, nm);
+    if (h->esz == 4)
+        k_gram<float, true><<<grid, 256, 0, s>>>(a);
+    else
+        k_gram<double, true><<<grid, 256, 0, s>>>(a);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------- factor
 // One workgroup per (matrix, rho index): M = sym(H) + sigma I + rho_j G, inverted in place by
 // Gauss-Jordan (SPD, no pivoting), float64.  LDS_MODE: M lives in LDS (n*n*8 B <= ~150 KB);
 // otherwise in a global scratch slab (L2-resident).  Output K_j in T, padded rows zeroed.
-template <typename T, bool LDS_MODE>
+template <typename T, bool LDS_MODE, typename TO = T>
 __global__ void __launch_bounds__(256) k_factor(SetupArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int n = a.n;
@@ -390,7 +437,7 @@ __global__ void __launch_bounds__(256) k_factor(SetupArgs a) {
     double* colb = (double*)smem_raw;            // [n]   column k before the sweep
     double* rowb = colb + n;                     // [n]   scaled pivot row
     double* M = LDS_MODE ? (rowb + n) : (a.fscratch + (size_t)blockIdx.x * n * n);
-    const T* Ht = (const T*)a.Ht + (size_t)mat * n * a.ldn;
+    const T* Ht = (const T*)a.Ht + (size_t)(a.mats_shared ? 0 : mat) * n * a.ldn;
     const double* G = a.G + (size_t)mat * n * n;
     const double rho = a.rhos[(a.wbase ? a.wbase[mat] : 0) + j];
     const int tid = threadIdx.x;
@@ -420,11 +467,11 @@ __global__ void __launch_bounds__(256) k_factor(SetupArgs a) {
         }
         __syncthreads();
     }
-    T* K = (T*)a.K + ((size_t)mat * a.kwin + j) * n * a.ldn;
+    TO* K = (TO*)a.K + ((size_t)mat * a.kwin + j) * n * a.ldn;
     for (int i = tid; i < n * a.ldn; i += 256) {
         int r = i / a.ldn, c = i % a.ldn;
         // symmetrise the rounded result so that column-oriented products see one matrix
-        K[i] = (c < n) ? (T)(0.5 * (M[(size_t)r * n + c] + M[(size_t)c * n + r])) : T(0);
+        K[i] = (c < n) ? (TO)(0.5 * (M[(size_t)r * n + c] + M[(size_t)c * n + r])) : TO(0);
     }
 }
 
@@ -437,7 +484,7 @@ __global__ void __launch_bounds__(256) k_factor(SetupArgs a) {
 constexpr int FB_N = 320, FB_P = 16;
 constexpr size_t fb_lds_bytes() { return ((size_t)FB_N * (FB_P + 1) + (size_t)FB_P * FB_N + (size_t)FB_P * (FB_P + 1) + 8) * sizeof(double); }
 
-template <typename T>
+template <typename T, typename TO = T>
 __global__ void __launch_bounds__(1024) k_factor_blk(SetupArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int P = FB_P, RT = FB_N / 32;
@@ -449,7 +496,7 @@ __global__ void __launch_bounds__(1024) k_factor_blk(SetupArgs a) {
     if (a.gate && *a.gate == 0) return;                                   // (uniform) fixed-pass protocol: nothing moved
     if (a.only && !a.only[mat]) return;
     double* M = a.fscratch + (size_t)blockIdx.x * n * n;
-    const T* Ht = (const T*)a.Ht + (size_t)mat * n * a.ldn;
+    const T* Ht = (const T*)a.Ht + (size_t)(a.mats_shared ? 0 : mat) * n * a.ldn;
     const double* G = a.G + (size_t)mat * n * n;
     const double rho = a.rhos[(a.wbase ? a.wbase[mat] : 0) + jslot];
     const int tid = threadIdx.x, ty = tid >> 5, tx = tid & 31;
@@ -556,18 +603,18 @@ __global__ void __launch_bounds__(1024) k_factor_blk(SetupArgs a) {
         }
         __syncthreads();
     }
-    T* K = (T*)a.K + ((size_t)mat * a.kwin + jslot) * n * a.ldn;
+    TO* K = (TO*)a.K + ((size_t)mat * a.kwin + jslot) * n * a.ldn;
     for (int i = tid; i < n * a.ldn; i += 1024) {
         const int r = i / a.ldn, c = i % a.ldn;
         // symmetrise the rounded result so that column-oriented products see one matrix
-        K[i] = (c < n) ? (T)(0.5 * (M[(size_t)r * n + c] + M[(size_t)c * n + r])) : T(0);
+        K[i] = (c < n) ? (TO)(0.5 * (M[(size_t)r * n + c] + M[(size_t)c * n + r])) : TO(0);
     }
 }
 
 // Fast path for n <= 128: same in-place Gauss-Jordan, but thread t owns column c = t & (CN-1) of the row slice
 // rs = t / CN (no integer division in the sweep, row k of the step in a register, column k broadcast from LDS).
 // CN = 64 or 128 columns (power of two >= n).
-template <typename T, int CN>
+template <typename T, int CN, typename TO = T>
 __global__ void __launch_bounds__(256) k_factor_fast(SetupArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     constexpr int RS = 256 / CN;                 // row slices
@@ -578,7 +625,7 @@ __global__ void __launch_bounds__(256) k_factor_fast(SetupArgs a) {
     double* colb = (double*)smem_raw;            // [n] column k before the sweep
     double* rowb = colb + n;                     // [n] scaled pivot row
     double* M = rowb + n;                        // [n][n] row-major (consecutive c -> consecutive banks); 2 WGs/CU at n = 100
-    const T* Ht = (const T*)a.Ht + (size_t)mat * n * a.ldn;
+    const T* Ht = (const T*)a.Ht + (size_t)(a.mats_shared ? 0 : mat) * n * a.ldn;
     const double* G = a.G + (size_t)mat * n * n;
     const double rho = a.rhos[(a.wbase ? a.wbase[mat] : 0) + j];
     const int tid = threadIdx.x, c = tid & (CN - 1), rs = tid / CN;
@@ -621,9 +668,9 @@ __global__ void __launch_bounds__(256) k_factor_fast(SetupArgs a) {
         }
         __syncthreads();
     }
-    T* K = (T*)a.K + ((size_t)mat * a.kwin + j) * n * a.ldn;
+    TO* K = (TO*)a.K + ((size_t)mat * a.kwin + j) * n * a.ldn;
     for (int r = rs; r < n; r += RS)
-        if (c < a.ldn) K[(size_t)r * a.ldn + c] = cin ? (T)(0.5 * (M[r * n + c] + M[c * n + r])) : T(0);
+        if (c < a.ldn) K[(size_t)r * a.ldn + c] = cin ? (TO)(0.5 * (M[r * n + c] + M[c * n + r])) : TO(0);
 }
 
 
@@ -647,7 +694,7 @@ __global__ void __launch_bounds__(256) k_factor_fast(SetupArgs a) {
 // TG: side of the thread grid.  16 (256 threads, four waves) for n <= 112; 8 (ONE wave per matrix, RT = 4: the barrier of a
 // step is free) for n <= 32 on the table path -- 256 threads on a 32 x 32 matrix hold 3 elements each and spend a step on its
 // barrier: 0.33 ms for the 40 960 inversions of the config-4 batch.
-template <typename T, int RT, int TG = 16>
+template <typename T, int RT, int TG = 16, typename TO = T>
 __global__ void __launch_bounds__(TG * TG, TG == 16 ? 4 : 8) k_factor_reg2(SetupArgs a) {
     constexpr int NMAX = TG * RT;
     __shared__ __attribute__((aligned(16))) double rowbuf[2][NMAX];
@@ -657,7 +704,7 @@ __global__ void __launch_bounds__(TG * TG, TG == 16 ? 4 : 8) k_factor_reg2(Setup
     if (a.gate && *a.gate == 0) return;                                   // (uniform) fixed-pass protocol: nothing moved
     if (a.only && !a.only[mat]) return;                                   // (uniform) re-factor of moved windows only
     const int tid = threadIdx.x, tx = tid & (TG - 1), ty = tid / TG;
-    const T* Ht = (const T*)a.Ht + (size_t)mat * n * a.ldn;
+    const T* Ht = (const T*)a.Ht + (size_t)(a.mats_shared ? 0 : mat) * n * a.ldn;
     const double* G = a.G + (size_t)mat * n * n;
     const double rho = a.rhos[(a.wbase ? a.wbase[mat] : 0) + jrho];
     double mreg[RT][RT];                                                  // blocks i <= j only
@@ -718,7 +765,7 @@ __global__ void __launch_bounds__(TG * TG, TG == 16 ? 4 : 8) k_factor_reg2(Setup
     // (i, (d - i) mod RT): an upper block comes from the thread's own registers, a lower block (i, j), i > j, is the
     // transpose of block (j, i) of thread (tx, ty) -- slot j of the same pass -- and a diagonal block averages the two
     // roundings of (r, c) and (c, r), which both exist there.
-    if constexpr (std::is_same<T, float>::value && TG == 16) {
+    if constexpr (std::is_same<TO, float>::value && TG == 16) {
         if (a.kp_img) {
             // Straight into the register image of k_admm_res2 (rqp_resident2.hip, k_pack_res2's layout):
             //   Kpack[mat][slot][pair = kp*KC + c][t = 64 w + lane][h] = K_j[CW w + KR rr + 2 kp + h][KC cc + c],  rr = lane >> 3, cc = lane & 7
@@ -771,7 +818,7 @@ __global__ void __launch_bounds__(TG * TG, TG == 16 ? 4 : 8) k_factor_reg2(Setup
             return;
         }
     }
-    T* K = (T*)a.K + ((size_t)mat * a.kwin + jrho) * n * a.ldn;
+    TO* K = (TO*)a.K + ((size_t)mat * a.kwin + jrho) * n * a.ldn;
 #pragma unroll
     for (int d = 0; d < RT; ++d) {
         __syncthreads();
@@ -789,70 +836,59 @@ __global__ void __launch_bounds__(TG * TG, TG == 16 ? 4 : 8) k_factor_reg2(Setup
             if (i < j) v = mreg[i][j];
             else if (i > j) v = tb[j][tx][ty];                            // M[c][r]: thread (tx, ty), block (j, i)
             else v = 0.5 * (mreg[i][i] + tb[i][tx][ty]);
-            if (r < n && c < a.ldn) K[(size_t)r * a.ldn + c] = (c < n) ? (T)(-v) : T(0);
+            if (r < n && c < a.ldn) K[(size_t)r * a.ldn + c] = (c < n) ? (TO)(-v) : TO(0);
         }
     }
 }
 
-template <typename T, int RT, int TG = 16>
+template <typename T, int RT, int TG = 16, typename TO = T>
 static hipError_t launch_factor_reg2(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
     // (kpack_direct: + a float stage of half of the register image's rows; 17 KB static + <= 23 KB: four workgroups still share a CU)
     const size_t stage = a.kp_img ? (size_t)2 * a.kp_cw * a.ldn * sizeof(float) : 0;
-    k_factor_reg2<T, RT, TG><<<a.nmat * a.kwin, TG * TG, stage, s>>>(a);
+    k_factor_reg2<T, RT, TG, TO><<<a.nmat * a.kwin, TG * TG, stage, s>>>(a);
     return hipGetLastError();
 }
 
-template <typename T, int CN>
+template <typename T, int CN, typename TO = T>
 static hipError_t launch_factor_fast(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
     const size_t lds = (2 * (size_t)h->n + (size_t)h->n * h->n) * sizeof(double);
-    hipError_t e = rqp_raise_lds_limit((const void*)k_factor_fast<T, CN>, (size_t)lds);
+    hipError_t e = rqp_raise_lds_limit((const void*)k_factor_fast<T, CN, TO>, (size_t)lds);
     if (e != hipSuccess) return e;
-    k_factor_fast<T, CN><<<a.nmat * a.kwin, 256, lds, s>>>(a);
+    k_factor_fast<T, CN, TO><<<a.nmat * a.kwin, 256, lds, s>>>(a);
     return hipGetLastError();
 }
 
-hipError_t rqp_launch_factor(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
+// T: the handle's dtype (Ht); TO: the type of K (T, or double for a.k_f64 -- solution polishing)
+template <typename T, typename TO>
+static hipError_t launch_factor_t(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
     const int n = h->n;
-    if (n <= 32 && !a.kp_img) return h->esz == 4 ? launch_factor_reg2<float, 4, 8>(h, a, s) : launch_factor_reg2<double, 4, 8>(h, a, s);
-    if (n <= 32) return h->esz == 4 ? launch_factor_reg2<float, 2>(h, a, s) : launch_factor_reg2<double, 2>(h, a, s);
-    if (n <= 64) return h->esz == 4 ? launch_factor_reg2<float, 4>(h, a, s) : launch_factor_reg2<double, 4>(h, a, s);
-    if (n <= 112 && h->ldn <= 112)
-        return h->esz == 4 ? launch_factor_reg2<float, 7>(h, a, s) : launch_factor_reg2<double, 7>(h, a, s);
-    if (n <= 64) return h->esz == 4 ? launch_factor_fast<float, 64>(h, a, s) : launch_factor_fast<double, 64>(h, a, s);
-    if (n <= 128 && h->ldn <= 128)
-        return h->esz == 4 ? launch_factor_fast<float, 128>(h, a, s) : launch_factor_fast<double, 128>(h, a, s);
+    if (n <= 32 && !a.kp_img) return launch_factor_reg2<T, 4, 8, TO>(h, a, s);
+    if (n <= 32) return launch_factor_reg2<T, 2, 16, TO>(h, a, s);
+    if (n <= 64) return launch_factor_reg2<T, 4, 16, TO>(h, a, s);
+    if (n <= 112 && h->ldn <= 112) return launch_factor_reg2<T, 7, 16, TO>(h, a, s);
+    if (n <= 128 && h->ldn <= 128) return launch_factor_fast<T, 128, TO>(h, a, s);
     const size_t lds_need = ((size_t)n * n + 2 * (size_t)n) * sizeof(double);
     const bool lds_mode = lds_need <= 160 * 1024 - 512;
     const int grid = a.nmat * a.kwin;
     hipError_t e;
     if (lds_mode) {
-        if (h->esz == 4) {
-            e = rqp_raise_lds_limit((const void*)k_factor<float, true>, (size_t)lds_need);
-            if (e != hipSuccess) return e;
-            k_factor<float, true><<<grid, 256, lds_need, s>>>(a);
-        } else {
-            e = rqp_raise_lds_limit((const void*)k_factor<double, true>, (size_t)lds_need);
-            if (e != hipSuccess) return e;
-            k_factor<double, true><<<grid, 256, lds_need, s>>>(a);
-        }
+        e = rqp_raise_lds_limit((const void*)k_factor<T, true, TO>, (size_t)lds_need);
+        if (e != hipSuccess) return e;
+        k_factor<T, true, TO><<<grid, 256, lds_need, s>>>(a);
     } else if (n <= FB_N) {
-        if (h->esz == 4) {
-            e = rqp_raise_lds_limit((const void*)k_factor_blk<float>, fb_lds_bytes());
-            if (e != hipSuccess) return e;
-            k_factor_blk<float><<<grid, 1024, fb_lds_bytes(), s>>>(a);
-        } else {
-            e = rqp_raise_lds_limit((const void*)k_factor_blk<double>, fb_lds_bytes());
-            if (e != hipSuccess) return e;
-            k_factor_blk<double><<<grid, 1024, fb_lds_bytes(), s>>>(a);
-        }
+        e = rqp_raise_lds_limit((const void*)k_factor_blk<T, TO>, fb_lds_bytes());
+        if (e != hipSuccess) return e;
+        k_factor_blk<T, TO><<<grid, 1024, fb_lds_bytes(), s>>>(a);
     } else {
         const size_t small = 2 * (size_t)n * sizeof(double);
-        if (h->esz == 4)
-            k_factor<float, false><<<grid, 256, small, s>>>(a);
-        else
-            k_factor<double, false><<<grid, 256, small, s>>>(a);
+        k_factor<T, false, TO><<<grid, 256, small, s>>>(a);
     }
     return hipGetLastError();
+}
+
+hipError_t rqp_launch_factor(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
+    if (h->esz == 8) return launch_factor_t<double, double>(h, a, s);
+    return a.k_f64 ? launch_factor_t<float, double>(h, a, s) : launch_factor_t<float, float>(h, a, s);
 }
 
 // ----------------------------------------------------------------------- state movers

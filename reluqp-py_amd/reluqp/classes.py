@@ -71,7 +71,10 @@ class Settings(object):
                  eps_rel=0.0,
                  eps_prim_inf=1e-4,
                  eps_dual_inf=1e-4,
-                 check_infeasibility=False):
+                 check_infeasibility=False,
+                 polish=False,
+                 delta=1e-6,
+                 polish_refine_iter=3):
         self.verbose = verbose
         self.warm_starting = warm_starting
         self.scaling = scaling
@@ -93,6 +96,10 @@ class Settings(object):
         self.eps_prim_inf = eps_prim_inf
         self.eps_dual_inf = eps_dual_inf
         self.check_infeasibility = check_infeasibility
+        # OSQP's solution polishing (names and defaults of OSQP's settings; include/rqp_abi.h rqp_set_polish)
+        self.polish = polish
+        self.delta = delta
+        self.polish_refine_iter = polish_refine_iter
 
 
 class Info(object):
@@ -123,6 +130,9 @@ class Info(object):
         self.rho_estimate = rho_estimate
         self.status_code = None
         self.rho_ind = None
+        # solution polishing: 1 accepted, -1 rejected, 0 not attempted (int32 tensor [batch] in a batched solve, an int
+        # otherwise; None when the handle polishes nothing)
+        self.status_polish = None
 
     # batched solves keep the exit codes on the device; the list of strings ("solved" /
     # "max_iters_reached", reluqpth.py:236,245) is built on first access (one device->host copy)
@@ -139,7 +149,8 @@ class Info(object):
 
 
 class Results(object):
-    """classes.py:91-95 (+ ``y``/``lam``: the dual of the returned state, Q7)."""
+    """classes.py:91-95 (+ ``y``/``lam``: the dual of the returned state, Q7; ``active``: the active set polish used,
+    int8 [batch, m] / [m] with -1 lower-active, +1 upper-active, 0 inactive -- None unless polish is on)."""
 
     def __init__(self, x=None, z=None, info: Info = None, y=None):
         self.x = x
@@ -147,3 +158,4 @@ class Results(object):
         self.y = y
         self.lam = y
         self.info = info
+        self.active = None

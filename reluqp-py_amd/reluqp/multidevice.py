@@ -76,6 +76,9 @@ class DeviceShards(object):
         # every child returns its own Results object: read the tensors before anything else is enqueued
         parts = [dict(x=r.x, z=r.z, y=r.y, it=r.info.iter, sc=r.info.status_code, ri=r.info.rho_ind, pri=r.info.pri_res,
                       dua=r.info.dua_res, rho=r.info.rho_estimate, obj=r.info.obj_val) for r in res]
+        if res[0].active is not None:                       # polish=True: status_polish [shard] and active [shard, m]
+            for p, r in zip(parts, res):
+                p["spol"], p["act"] = r.info.status_polish, r.active
         self._wait()
         out = {k: self._gather([p[k] for p in parts]) for k in parts[0]}
         torch.cuda.current_stream(self.devices[0]).synchronize()

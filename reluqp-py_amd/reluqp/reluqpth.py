@@ -31,6 +31,7 @@ from reluqp import _cabi
 from reluqp.classes import QP, Info, Results, Settings, _as_tensor, _default_device
 
 _CHANGEABLE = ("max_iter", "eps_abs", "verbose", "check_interval", "eps_rel", "check_infeasibility")
+_POLISH = ("polish", "delta", "polish_refine_iter")     # changeable only on a handle set up with polish=True
 _FROZEN = ("rho", "rho_min", "rho_max", "sigma", "adaptive_rho", "adaptive_rho_interval",
            "adaptive_rho_tolerance")
 
@@ -75,6 +76,7 @@ class ReLU_QP(object):
         self.synchronous = True
         self.last_kernel_time = None
         self._shards = None           # setup(devices=[...]): one child solver per device (reluqp/multidevice.py)
+        self._polish_reserved = False  # setup(polish=True): the handle holds the polish workspace (rqp_set_polish)
 
     # ------------------------------------------------------------------ helpers
     def _stream(self):
@@ -146,7 +148,10 @@ class ReLU_QP(object):
               devices=None,
               low_memory=False,
               full_ladder=False,
-              graph_passes=None):
+              graph_passes=None,
+              polish=False,
+              delta=1e-6,
+              polish_refine_iter=3):
         """
         Setup ReLU-QP solver problem of the form
 
@@ -178,6 +183,11 @@ class ReLU_QP(object):
         solve needs (``window_pass_bound(max_iter, check_interval)`` always does; 2-4 are typical), an instance still waiting
         after P passes reports status "window_passes_exhausted".  No effect on handles that are not windowed (full_ladder=True,
         shared H and A, batches below 32): they are capturable as they are.
+        ``polish=True`` (OSQP's solution polishing, C-ABI rqp_set_polish; ``delta`` and ``polish_refine_iter`` are OSQP's
+        names and defaults): every solved instance solves the reduced KKT system of the active set its ADMM iterate
+        suggests, in float64, refines it and keeps it when its residuals beat the ADMM ones (``info.status_polish`` 1;
+        -1 rejected, 0 not solved).  The ADMM state, iteration counts and rho indices are those of a solve without polish;
+        ``results.active`` holds the active set.  Reserved at setup: ``update_settings(polish=...)`` needs it.
         """
         if devices is not None:
             from reluqp.multidevice import DeviceShards
@@ -190,7 +200,7 @@ class ReLU_QP(object):
                       check_interval=check_interval, precision=precision, eq_tol=eq_tol, eps_rel=eps_rel,
                       check_infeasibility=check_infeasibility, eps_prim_inf=eps_prim_inf, eps_dual_inf=eps_dual_inf,
                       kernel=kernel, iterate_dtype=iterate_dtype, low_memory=low_memory, full_ladder=full_ladder,
-                      graph_passes=graph_passes)
+                      graph_passes=graph_passes, polish=polish, delta=delta, polish_refine_iter=polish_refine_iter)
             self._shards = DeviceShards(ReLU_QP, list(devices), H, g, A, l, u, kw)
             first = self._shards.children[0]
             self.settings, self.QP, self.layers, self._rhos = first.settings, first.QP, first.layers, first._rhos
@@ -216,7 +226,9 @@ class ReLU_QP(object):
                                  eps_abs=eps_abs, eq_tol=eq_tol, check_interval=check_interval,
                                  device=device, precision=precision, eps_rel=eps_rel,
                                  eps_prim_inf=eps_prim_inf, eps_dual_inf=eps_dual_inf,
-                                 check_infeasibility=check_infeasibility)
+                                 check_infeasibility=check_infeasibility, polish=bool(polish), delta=float(delta),
+                                 polish_refine_iter=int(polish_refine_iter))
+        self._polish_reserved = bool(polish)
         if kernel not in _cabi.KERNELS:
             raise ValueError("kernel must be one of %s" % sorted(_cabi.KERNELS))
         if iterate_dtype not in (None, precision, torch.float16, torch.bfloat16):
@@ -240,6 +252,8 @@ class ReLU_QP(object):
             self._h = h
             if graph_passes is not None:
                 _cabi.check(h, lib.rqp_set_window_passes(h, int(graph_passes)), "rqp_set_window_passes")
+            if polish:
+                _cabi.check(h, lib.rqp_set_polish(h, 1, float(delta), int(polish_refine_iter)), "rqp_set_polish")
             _cabi.check(h, lib.rqp_setup(h, _cabi.ptr(qp.H), _cabi.ptr(qp.g), _cabi.ptr(qp.A), _cabi.ptr(qp.l),
                                          _cabi.ptr(qp.u), self._stream()), "rqp_setup")
             cnt = ctypes.c_int32()
@@ -344,15 +358,21 @@ class ReLU_QP(object):
         Update ReLU-QP solver settings
 
         It is possible to change: 'max_iter', 'eps_abs', 'verbose', 'check_interval'
-        (reference reluqpth.py:185-199; the whitelist typo "eps_ab" is tolerated, Q8)
+        (reference reluqpth.py:185-199; the whitelist typo "eps_ab" is tolerated, Q8), and on a handle set up with
+        ``polish=True``: 'polish', 'delta', 'polish_refine_iter'
         """
         if self._shards:
             return self._shards.update_settings(**kwargs)
         self._need_setup()
+        pol = {}
         for key, value in kwargs.items():
             if key == "eps_ab":
                 key = "eps_abs"
-            if key in _CHANGEABLE:
+            if key in _POLISH:
+                if not self._polish_reserved:
+                    raise ValueError("Cannot change {} on a solver set up without polish=True".format(key))
+                pol[key] = value
+            elif key in _CHANGEABLE:
                 setattr(self.settings, key, value)
             elif key in _FROZEN:
                 raise ValueError("Cannot change {} after setup".format(key))
@@ -360,6 +380,15 @@ class ReLU_QP(object):
                 raise ValueError("Invalid setting: {}".format(key))
         cs = self._csettings()
         _cabi.check(self._h, _cabi.load().rqp_update_settings(self._h, ctypes.byref(cs)), "rqp_update_settings")
+        if pol:
+            st = self.settings
+            new = dict(polish=bool(pol.get("polish", st.polish)), delta=float(pol.get("delta", st.delta)),
+                       polish_refine_iter=int(pol.get("polish_refine_iter", st.polish_refine_iter)))
+            with torch.cuda.device(st.device):
+                _cabi.check(self._h, _cabi.load().rqp_set_polish(self._h, int(new["polish"]), new["delta"],
+                                                                 new["polish_refine_iter"]), "rqp_set_polish")
+            for k, v in new.items():
+                setattr(st, k, v)
 
     # -------------------------------------------------------------------- solve
     def solve(self):
@@ -400,6 +429,12 @@ class ReLU_QP(object):
                 k0.record(stream)
             _cabi.check(self._h, lib.rqp_solve(self._h, _cabi.ptr(x), _cabi.ptr(z), _cabi.ptr(lam),
                                                ctypes.byref(ci), ctypes.c_void_p(stream.cuda_stream)), "rqp_solve")
+            pol = None
+            if st.polish:                # status_polish [B] + active [B, m] of this solve (device copies, stream-ordered)
+                pol = torch.empty(B * (4 + m), device=dev, dtype=torch.int8)
+                _cabi.check(self._h, lib.rqp_get_polish(self._h, pol[:4 * B].data_ptr(), pol[4 * B:].data_ptr(),
+                                                        ctypes.c_void_p(stream.cuda_stream)), "rqp_get_polish")
+                pol = (pol[:4 * B].view(torch.int32), pol[4 * B:].view(B, m))
             if timed:
                 k1.record(stream)
                 k1.synchronize()
@@ -411,7 +446,7 @@ class ReLU_QP(object):
         self.last_trace = trace      # [batch][checks][pri, dua, rho_estimate, rho_ind before the move]
         if st.verbose:
             self._print_trace(trace)
-        self._update_results(x, z, lam, ints, dbls, run_time)
+        self._update_results(x, z, lam, ints, dbls, run_time, pol)
         return self.results
 
     def _print_trace(self, trace):
@@ -422,10 +457,16 @@ class ReLU_QP(object):
             print('Iter: {}, rho: {:.2e}, res_p: {:.2e}, res_d: {:.2e}'.format(
                 (c + 1) * self.settings.check_interval, tr[c, 2], tr[c, 0], tr[c, 1]))
 
-    def _update_results(self, x, z, lam, ints, dbls, run_time):
+    def _update_results(self, x, z, lam, ints, dbls, run_time, pol=None):
         """Update results and info (reference reluqpth.py:278-305)."""
         qp, prec = self.QP, self.settings.precision
         info = self.results.info
+        if pol is None:
+            info.status_polish, self.results.active = None, None
+        elif qp.batched:
+            info.status_polish, self.results.active = pol
+        else:
+            info.status_polish, self.results.active = int(pol[0][0]), pol[1][0]
         if qp.batched:
             self.results.x, self.results.z, self.results.y = x, z, lam
             info.iter = ints[0]
@@ -461,6 +502,7 @@ class ReLU_QP(object):
         self.results.x, self.results.z, self.results.y = o["x"], o["z"], o["y"]
         self.results.lam = self.results.y
         info.iter, info.status_code, info.status, info.rho_ind = o["it"], o["sc"], None, o["ri"]
+        info.status_polish, self.results.active = o.get("spol"), o.get("act")
         # per-instance scalars stay float64 as the kernels wrote them -- the same dtypes as the single-device batch path
         info.pri_res, info.dua_res = o["pri"], o["dua"]
         info.rho_estimate, info.obj_val = o["rho"], o["obj"]
