@@ -354,6 +354,52 @@ int rqp_set_adjoint(rqp_handle* h, int32_t enable, double delta, int32_t refine_
  * RQP_ERR_STATE: the handle is not set up, or was set up without rqp_set_adjoint.                                            */
 int rqp_adjoint(rqp_handle* h, const rqp_adjoint_io* io, void* stream);
 
+/* Forward-mode sensitivities of a solve (JVPs; DESIGN.md section 5 "Forward sensitivities").  At a solution with
+ * sym(H) x + g + A' y = 0 and active set a (classified and signed as rqp_adjoint does; ybar = y on a, 0 elsewhere), the
+ * tangents (dH, dg, dA, dl, du) of the data give, per direction,
+ *     [[sym(H), A_a'], [A_a, 0]] [dx; dy_a] = [-(sym(dH) x + dg + dA' ybar);  db_a - dA_a x],   dy = 0 off a,
+ *     dz = A dx + dA x,
+ * with db_i = dl_i on lower-active rows and du_i on upper-active ones (an equality row takes the bound the sign of y names).
+ * The system is the adjoint's, solved the same way (regularised by delta, refine_iter refinement steps; the adjoint's delta
+ * and refine_iter, rqp_set_adjoint), for blocks of 16 directions against one M^-1 per instance.  A degenerate active set
+ * gives the delta-regularised answer; sens_res shows how far it is from solving the unregularised system.
+ * Every array has the direction axis LAST: dg [batch][n][ndir], dl / du [batch][m][ndir], dH [batch][n][n][ndir],
+ * dA [batch][m][n][ndir]; a tangent whose bit is set in shared_tangents has no batch axis ([n][ndir], ...) and is used by
+ * every instance.  Column j of every output depends on direction j alone: bitwise the same in any ndir.
+ * DEVICE pointers in dims.dtype unless typed otherwise; arithmetic is float64.                                              */
+#define RQP_SENS_SHARED_DH 1
+#define RQP_SENS_SHARED_DG 2
+#define RQP_SENS_SHARED_DA 4
+#define RQP_SENS_SHARED_DL 8
+#define RQP_SENS_SHARED_DU 16
+typedef struct rqp_sensitivity_io {
+    const void *H, *A;           /* the caller's matrices, shapes and layout as in rqp_setup ([n][n] / [m][n] when shared) */
+    const void *l, *u;           /* [batch][m]                                                                           */
+    const void *x, *z, *y;       /* the solution to differentiate at: [batch][n], [batch][m], [batch][m]                 */
+    const int32_t* status;       /* [batch] rqp_status of that solve, NULL = all treated as solved                        */
+    const int8_t* active;        /* [batch][m] -1 / 0 / +1, NULL = classified from (z, y, l, u) with polish's rule        */
+    int32_t ndir;                /* directions (>= 1)                                                                     */
+    int32_t shared_tangents;     /* RQP_SENS_SHARED_* bits: those tangents have no batch axis                             */
+    const void *dH, *dg, *dA, *dl, *du; /* tangents, direction axis last; NULL = zero                                     */
+    void *dx;                    /* [batch][n][ndir] output (required)                                                   */
+    void *dy, *dz;               /* [batch][m][ndir] outputs, NULL to skip                                               */
+    int8_t* active_out;          /* [batch][m] the set used, NULL to skip                                                 */
+    int32_t* sens_status;        /* [batch] 1 computed, 0 skipped (status != solved: every output of it is 0)             */
+    double* sens_res;            /* [batch] max over directions of the relative residual (NaN when skipped)              */
+} rqp_sensitivity_io;
+
+/* Reserve (before rqp_setup) the sensitivities' workspace: the adjoint's packed matrices, G_a, M^-1 (shared with the
+ * adjoint and polish when those are reserved too), the active-row lists and one chunk of float64 direction blocks.
+ * Handles without it allocate nothing for it.  After setup: RQP_OK if the state matches, else RQP_ERR_STATE.          */
+int rqp_set_sensitivity(rqp_handle* h, int32_t enable);
+
+/* Sensitivities of a solve of this handle's shape at the caller's data (io); as rqp_adjoint, nothing of the handle's state
+ * is read.  A fixed, data-independent chain on `stream` (classify, pack; per chunk masked gram, factor, then one
+ * right-hand-side and one solve launch per block of 16 directions); capturable in a HIP graph.  RQP_ERR_ARG: h, io,
+ * io->dx, x, y, H or A NULL, ndir < 1, or z, l or u NULL without io->active.  RQP_ERR_STATE: the handle is not set up,
+ * or was set up without rqp_set_sensitivity.                                                                            */
+int rqp_sensitivity(rqp_handle* h, const rqp_sensitivity_io* io, void* stream);
+
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);
 

@@ -101,7 +101,8 @@ void free_ws(rqp_handle* h) {
                      (void**)&h->ncont_d, (void**)&h->polish_G, (void**)&h->polish_Minv, (void**)&h->polish_rho,
                      (void**)&h->polish_status, (void**)&h->polish_act, (void**)&h->polish_flag, (void**)&h->polish_st_in,
                      (void**)&h->polish_res_in, &h->adj_Ht, &h->adj_A, (void**)&h->adj_G_own, (void**)&h->adj_Minv_own,
-                     (void**)&h->adj_rho, (void**)&h->adj_flag, (void**)&h->adj_act, (void**)&h->adj_rows};
+                     (void**)&h->adj_rho, (void**)&h->adj_flag, (void**)&h->adj_act, (void**)&h->adj_rows,
+                     (void**)&h->sens_idx, (void**)&h->sens_pos, (void**)&h->sens_na, (void**)&h->sens_ws};
     // hipFree is one of the calls that invalidate a stream capture in progress (global / thread-local capture modes).  A handle
     // may be destroyed while this thread captures something else (a Python finaliser, an explicit `del`): free under the
     // relaxed mode, which exists for exactly this.
@@ -491,11 +492,16 @@ int rqp_setup(rqp_handle* h, const void* H, const void* g, const void* A, const 
         HIP_TRY(h, hipMalloc((void**)&h->polish_res_in, 3 * B * sizeof(double)));
         HIP_TRY(h, hipStreamSynchronize(s));          // (idel lives on this stack frame)
     }
-    if (h->adj_reserved) {      // adjoint (rqp_adjoint.hip): packed caller matrices, G_a and M^-1 per chunk, per-instance rows
-        if (rqp_adjoint_lds_bytes(h) > 160 * 1024) {
-            free_ws(h);
-            return fail_unsupported(h, "rqp_setup: the adjoint needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
-        }
+    if (h->adj_reserved && rqp_adjoint_lds_bytes(h) > 160 * 1024) {
+        free_ws(h);
+        return fail_unsupported(h, "rqp_setup: the adjoint needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
+    }
+    if (h->sens_reserved && rqp_sens_lds_bytes(h) > 160 * 1024) {
+        free_ws(h);
+        return fail_unsupported(h, "rqp_setup: the sensitivities need 384 ceil16(n) + 2 KB of LDS, above 160 KB");
+    }
+    if (h->adj_reserved || h->sens_reserved) {
+        // adjoint (rqp_adjoint.hip) and forward sensitivities (rqp_sens.hip): packed caller matrices, G_a and M^-1 per chunk
         h->adj_chunk = rqp_polish_chunk(h);
         const size_t pc = h->adj_chunk, pm = h->dims.shared_mats ? 1 : pc;
         HIP_TRY(h, hipMalloc(&h->adj_Ht, pm * n * h->ldn * e));
@@ -514,7 +520,14 @@ int rqp_setup(rqp_handle* h, const void* H, const void* g, const void* A, const 
         HIP_TRY(h, hipMemcpyAsync(h->adj_rho, &idel, sizeof(double), hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipMalloc((void**)&h->adj_flag, B * sizeof(int32_t)));
         HIP_TRY(h, hipMalloc((void**)&h->adj_act, B * m));
-        HIP_TRY(h, hipMalloc((void**)&h->adj_rows, B * (2 * n + 2 * m) * sizeof(double)));
+        if (h->adj_reserved)                    // per-instance rows of the matrix gradients
+            HIP_TRY(h, hipMalloc((void**)&h->adj_rows, B * (2 * n + 2 * m) * sizeof(double)));
+        if (h->sens_reserved) {                 // active-row lists, one chunk of direction blocks
+            HIP_TRY(h, hipMalloc((void**)&h->sens_idx, B * m * sizeof(int32_t)));
+            HIP_TRY(h, hipMalloc((void**)&h->sens_pos, B * m * sizeof(int32_t)));
+            HIP_TRY(h, hipMalloc((void**)&h->sens_na, B * sizeof(int32_t)));
+            HIP_TRY(h, hipMalloc((void**)&h->sens_ws, pc * rqp_sens_ws_doubles(h) * sizeof(double)));
+        }
         HIP_TRY(h, hipStreamSynchronize(s));          // (idel lives on this stack frame)
     }
     h->handoff_cols = 0;
@@ -950,7 +963,7 @@ int rqp_set_adjoint(rqp_handle* h, int32_t enable, double delta, int32_t refine_
         h->adj_refine = refine_iter;
         return RQP_OK;
     }
-    if (!h->adj_reserved)
+    if (!h->adj_reserved && !h->sens_reserved)      // (delta and refine_iter are the sensitivities' too)
         return fail_state(h, "rqp_set_adjoint: the handle was set up without the adjoint (call rqp_set_adjoint before rqp_setup)");
     HIP_TRY(h, hipSetDevice(h->device));
     if (delta != h->adj_delta) {
@@ -971,6 +984,30 @@ int rqp_adjoint(rqp_handle* h, const rqp_adjoint_io* io, void* stream) {
         return fail_state(h, "rqp_adjoint: the handle was not set up with the adjoint (rqp_set_adjoint before rqp_setup)");
     HIP_TRY(h, hipSetDevice(h->device));
     HIP_TRY(h, rqp_launch_adjoint(h, *io, (hipStream_t)stream));
+    return RQP_OK;
+}
+
+int rqp_set_sensitivity(rqp_handle* h, int32_t enable) {
+    if (!h) return RQP_ERR_ARG;
+    if (!h->is_setup) {                             // before rqp_setup: reserve (or not) the workspace
+        h->sens_reserved = enable != 0;
+        return RQP_OK;
+    }
+    if (h->sens_reserved != (enable != 0))
+        return fail_state(h, "rqp_set_sensitivity: the reservation is fixed at rqp_setup (call rqp_set_sensitivity before it)");
+    return RQP_OK;
+}
+
+int rqp_sensitivity(rqp_handle* h, const rqp_sensitivity_io* io, void* stream) {
+    if (!h || !io) return RQP_ERR_ARG;
+    if (!io->dx || !io->x || !io->y || !io->H || !io->A) return fail_arg(h, "rqp_sensitivity: dx, x, y, H and A are required");
+    if (io->ndir < 1) return fail_arg(h, "rqp_sensitivity: ndir < 1");
+    if (!io->active && (!io->z || !io->l || !io->u))
+        return fail_arg(h, "rqp_sensitivity: z, l and u are required when no active set is given");
+    if (!h->is_setup || !h->sens_reserved)
+        return fail_state(h, "rqp_sensitivity: the handle was not set up with sensitivities (rqp_set_sensitivity before rqp_setup)");
+    HIP_TRY(h, hipSetDevice(h->device));
+    HIP_TRY(h, rqp_launch_sensitivity(h, *io, (hipStream_t)stream));
     return RQP_OK;
 }
 

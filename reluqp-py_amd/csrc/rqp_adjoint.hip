@@ -401,6 +401,11 @@ hipError_t launch_adjoint_t(rqp_handle* h, const rqp_adjoint_io& io, hipStream_t
 
 size_t rqp_adjoint_lds_bytes(const rqp_handle* h) { return (4 * (size_t)h->n + 4 * (size_t)h->m + PT + 8) * sizeof(double); }
 
+hipError_t rqp_launch_adj_pack(const rqp_handle* h, int cnt, const void* H, const void* A, hipStream_t s) {
+    if (h->esz == 4) return launch_pack<float>(h, cnt, (const float*)H, (const float*)A, (float*)h->adj_Ht, (float*)h->adj_A, s);
+    return launch_pack<double>(h, cnt, (const double*)H, (const double*)A, (double*)h->adj_Ht, (double*)h->adj_A, s);
+}
+
 hipError_t rqp_launch_adjoint(rqp_handle* h, const rqp_adjoint_io& io, hipStream_t s) {
     return h->esz == 4 ? launch_adjoint_t<float>(h, io, s) : launch_adjoint_t<double>(h, io, s);
 }

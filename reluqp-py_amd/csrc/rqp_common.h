@@ -136,6 +136,15 @@ struct rqp_handle {
     int8_t* adj_act = nullptr;          // [B][m] the active set used
     double* adj_rows = nullptr;         // [B][2 n + 2 m]: rx, x, ry, ybar (zero on skipped instances)
 
+    // Forward sensitivities (rqp_set_sensitivity, rqp_sens.hip): reserved at setup.  They share the adjoint's packed matrices,
+    // G_a, M^-1, 1 / delta, flag and active set (allocated for either reservation; delta and refine_iter are adj_delta /
+    // adj_refine) and add the active-row lists and one chunk of float64 direction blocks ([adj_chunk][n + 4 m][16]).
+    bool sens_reserved = false;
+    int32_t* sens_idx = nullptr;        // [B][m] active rows in ascending order (sens_na[b] of them)
+    int32_t* sens_pos = nullptr;        // [B][m] row -> position in sens_idx, -1 off the active set
+    int32_t* sens_na = nullptr;         // [B]
+    double* sens_ws = nullptr;          // [adj_chunk][n + 4 m][16]: r1, r2, dy_a, A_a dx, dA x
+
     const char* kernel_name = "generic";
     std::string err;
 };
@@ -246,6 +255,13 @@ hipError_t rqp_launch_polish(rqp_handle* h, const SolveArgs& a, hipStream_t s);
 // adjoint (rqp_adjoint.hip): workspace sizing at setup, LDS of k_adjoint, and the whole fixed chain of rqp_adjoint
 size_t rqp_adjoint_lds_bytes(const rqp_handle* h);
 hipError_t rqp_launch_adjoint(rqp_handle* h, const rqp_adjoint_io& io, hipStream_t s);
+// the adjoint's packer: sym(H) and A of `cnt` caller matrices into adj_Ht / adj_A (pitch ldn)
+hipError_t rqp_launch_adj_pack(const rqp_handle* h, int cnt, const void* H, const void* A, hipStream_t s);
+
+// forward sensitivities (rqp_sens.hip): LDS of k_sens_solve, direction-block workspace per instance, the fixed chain
+size_t rqp_sens_lds_bytes(const rqp_handle* h);
+size_t rqp_sens_ws_doubles(const rqp_handle* h);
+hipError_t rqp_launch_sensitivity(rqp_handle* h, const rqp_sensitivity_io& io, hipStream_t s);
 
 // one-time launch preparation (dynamic-LDS function attributes), called from rqp_setup for the selected kernels
 hipError_t rqp_prepare_generic(const rqp_handle* h);

@@ -24,7 +24,7 @@ ABI_SYMBOLS = (
     "rqp_default_settings", "rqp_create", "rqp_setup", "rqp_update", "rqp_update_mats", "rqp_update_affine",
     "rqp_update_settings",
     "rqp_warm_start", "rqp_clear_primal_dual", "rqp_solve", "rqp_iterate", "rqp_compute_residuals",
-    "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
+    "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
     "rqp_last_error", "rqp_version",
 )
 
@@ -58,6 +58,17 @@ class AdjointIO(ctypes.Structure):
     """struct rqp_adjoint_io: device pointers (None = NULL)."""
     _fields_ = [(f, ctypes.c_void_p) for f in ("H", "A", "l", "u", "x", "z", "y", "status", "active", "dx", "dy",
                                                 "dH", "dg", "dA", "dl", "du", "active_out", "adj_status", "adj_res")]
+
+
+SENS_SHARED = {"dH": 1, "dg": 2, "dA": 4, "dl": 8, "du": 16}     # RQP_SENS_SHARED_* (rqp_sensitivity_io.shared_tangents)
+
+
+class SensitivityIO(ctypes.Structure):
+    """struct rqp_sensitivity_io: device pointers (None = NULL), ndir and the shared-tangent bits."""
+    _fields_ = ([(f, ctypes.c_void_p) for f in ("H", "A", "l", "u", "x", "z", "y", "status", "active")] +
+                [("ndir", ctypes.c_int32), ("shared_tangents", ctypes.c_int32)] +
+                [(f, ctypes.c_void_p) for f in ("dH", "dg", "dA", "dl", "du", "dx", "dy", "dz", "active_out", "sens_status",
+                                                "sens_res")])
 
 
 class CInfo(ctypes.Structure):
@@ -113,6 +124,8 @@ def load():
         "rqp_get_polish": (ctypes.c_int, [H, vp, vp, vp]),
         "rqp_set_adjoint": (ctypes.c_int, [H, i32, dbl, i32]),
         "rqp_adjoint": (ctypes.c_int, [H, ctypes.POINTER(AdjointIO), vp]),
+        "rqp_set_sensitivity": (ctypes.c_int, [H, i32]),
+        "rqp_sensitivity": (ctypes.c_int, [H, ctypes.POINTER(SensitivityIO), vp]),
         "rqp_kernel_name": (ctypes.c_char_p, [H]),
         "rqp_destroy": (ctypes.c_int, [H]),
         "rqp_strerror": (ctypes.c_char_p, [ctypes.c_int]),

@@ -6,6 +6,8 @@ for a batch on the GPU and back-propagates through the solution with the library
 section 5 "Adjoint (autograd)").  The backward pass solves the reduced KKT system of each instance's active set; it is
 exact where the active set is strictly complementary and non-degenerate, the one-sided derivative on rows sitting exactly on
 a bound with a zero multiplier, and the delta-regularised solution on degenerate active sets (``Gradients.residual``).
+With ``ReLUQPLayer(sensitivity=True)`` forward-mode AD (``torch.autograd.forward_ad``) works too: ``QPFunction.jvp`` pushes the
+input tangents through the same reduced KKT system (C-ABI rqp_sensitivity, DESIGN.md section 5 "Forward sensitivities").
 
 Host code is plumbing: handle bookkeeping, reshapes and casts.  The batch sums of broadcast inputs are the only reductions.
 """
@@ -27,8 +29,9 @@ class QPFunction(torch.autograd.Function):
         qp = solver.QP
         x, y, z = res.x.clone(), res.y.clone(), res.z.clone()
         status = torch.as_tensor(res.info.status_code).to(device=x.device, dtype=torch.int32).reshape(-1).clone()
-        ctx.solver, ctx.shapes = solver, shapes
+        ctx.solver, ctx.shapes, ctx.return_z = solver, shapes, return_z
         ctx.save_for_backward(qp.H, qp.A, qp.l, qp.u, x, z, y, status)
+        ctx.save_for_forward(qp.H, qp.A, qp.l, qp.u, x, z, y, status)
         ctx.mark_non_differentiable(z)
         return (x, y, z) if return_z else (x, y)
 
@@ -55,6 +58,21 @@ class QPFunction(torch.autograd.Function):
         return tuple(grads)
 
 
+    @staticmethod
+    def jvp(ctx, _layer, _return_z, dH, dg, dA, dl, du):
+        """Tangents of (x, y) along the input tangents (None for z): one direction, through ReLU_QP.jvp_at.  A tangent of an
+        input without the batch axis (shared H / A, or g / l / u broadcast over the batch) is passed as a shared one."""
+        H, A, l, u, x, z, y, status = ctx.saved_tensors
+        solver = ctx.solver
+        if not solver._sens_reserved:
+            raise RuntimeError("forward-mode AD through ReLUQPLayer needs ReLUQPLayer(sensitivity=True)")
+        prec = x.dtype
+        tan = {k: None if t is None else t.to(prec) for k, t in zip(_NAMES, (dH, dg, dA, dl, du))}
+        s = solver.jvp_at(H, A, l, u, x, z, y, status=status, **tan)
+        dx, dy = s.dx.reshape(x.shape), s.dy.reshape(y.shape)
+        return (dx, dy, None) if ctx.return_z else (dx, dy)
+
+
 class ReLUQPLayer(torch.nn.Module):
     """A batched QP as a differentiable module.  ``forward(H, g, A, l, u)`` returns ``(x, y)`` (``(x, y, z)`` with
     ``return_z=True``).  H [n, n] / A [m, n] are shared by the batch, [B, n, n] / [B, m, n] per instance; g, l, u are [B, .]
@@ -63,7 +81,8 @@ class ReLUQPLayer(torch.nn.Module):
     One solver handle is kept per (shapes, dtype, device); ``setup`` runs on first use, ``update(Hx=, Ax=)`` when H or A is
     not the previous call's tensor (another object, or modified in place), then ``update(g, l, u)`` and ``solve()``.  The
     keyword arguments are those of ``ReLU_QP.setup`` (defaults here: ``differentiable=True``, ``polish=True``,
-    ``precision`` = the dtype of g)."""
+    ``precision`` = the dtype of g).  ``sensitivity=True`` also reserves the forward sensitivities: forward-mode AD
+    (``torch.autograd.forward_ad``, ``gradcheck(..., check_forward_ad=True)``) then works through the layer."""
 
     def __init__(self, return_z=False, **setup_kwargs):
         super().__init__()

@@ -206,6 +206,35 @@ class LinearMPC(object):
         return dict(gmap=t(self.g_x0), lumap=t(self.lu_x0), ladd=t(self.l_add), uadd=t(self.u_add),
                     Aclt=t((self.Ad - self.Bd @ self.K).T), Bdt=t(self.Bd.T))
 
+    def feedback_gain(self, x):
+        """Local feedback gain d u0* / d x0 of the handle's last solve: a device tensor [B, nu, nx], and the per-instance
+        status of the sensitivities (1 computed, 0: that solve did not succeed, its gain is then the condensed form's -K or 0).
+        ``x`` [B, nx] are the states that solve was for.  The solver must be set up with ``sensitivity=True`` (solver_kw).
+        One rqp_sensitivity call with ndir = nx: the device maps of the closed loop are the shared tangents (dg = gmap,
+        dl = du = lumap); l and u are rebuilt from x, so this also follows simulate_device / update_affine.  Every equality
+        row (l == u: the sparse form's dynamics) is active, also where its multiplier rounds to zero.  The condensed form's
+        input is u0 = v0 - K x0: its gain is d v0 / d x0 - K."""
+        import torch
+        s = self.solver
+        if s is None or not self._ready:
+            raise RuntimeError("feedback_gain: solve first (step / simulate_device)")
+        st, res = s.settings, s.results
+        mp = self._device_maps(st.device, st.precision)
+        x = torch.as_tensor(np.atleast_2d(x) if not torch.is_tensor(x) else x, device=st.device, dtype=st.precision)
+        shift = x @ mp["lumap"].T
+        l, u = mp["ladd"] + shift, mp["uadd"] + shift
+        # the adjoint's classification in the caller's units, equality rows forced active (side: the sign of y)
+        z, y = res.z, res.y
+        act = torch.where(z - l < -y, -1, torch.where(u - z < y, 1, 0))
+        act = torch.where(l == u, torch.where(y > 0, 1, -1), act).to(torch.int8)
+        dx, _, _, status, _, _ = s._sens_call(s.QP.H, s.QP.A, l, u, res.x, z, y,
+                                              dict(dg=(mp["gmap"], True), dl=(mp["lumap"], True), du=(mp["lumap"], True)),
+                                              self.nx, status=res.info.status_code, active=act, want_dz=False)
+        gain = dx[:, :self.nu, :]
+        if self.form == "condensed":
+            gain = gain - torch.as_tensor(self.K, device=st.device, dtype=st.precision)
+        return gain, status
+
     def simulate_device(self, x0, steps, device, dtype):
         """Closed loop with every per-step map on the device (no host round trip per control step):
         g = G x, l/u = l_add/u_add + LU x (rqp_update_affine), warm solve, x+ = (Ad - Bd K) x + Bd v0 with v0 the first

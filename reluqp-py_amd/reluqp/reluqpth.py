@@ -40,6 +40,10 @@ _FROZEN = ("rho", "rho_min", "rho_max", "sigma", "adaptive_rho", "adaptive_rho_i
 # ReLU_QP.adjoint / adjoint_at: gradients of a scalar loss with respect to the problem data, and per instance the adjoint's
 # status (1 computed, 0 skipped: not solved), relative residual (NaN when skipped) and the active set used.
 Gradients = collections.namedtuple("Gradients", "dH dg dA dl du status residual active")
+# ReLU_QP.jvp / jvp_at: tangents of the solution (x, y, z) along directions of the problem data, and per instance the status
+# (1 computed, 0 skipped), the maximum relative residual over the directions (NaN when skipped) and the active set used.
+Sensitivities = collections.namedtuple("Sensitivities", "dx dy dz status residual active")
+_TANGENTS = ("dH", "dg", "dA", "dl", "du")
 
 
 def window_pass_bound(max_iter, check_interval):
@@ -84,6 +88,7 @@ class ReLU_QP(object):
         self._shards = None           # setup(devices=[...]): one child solver per device (reluqp/multidevice.py)
         self._polish_reserved = False  # setup(polish=True): the handle holds the polish workspace (rqp_set_polish)
         self._adj_reserved = False    # setup(differentiable=True): the handle holds the adjoint workspace (rqp_set_adjoint)
+        self._sens_reserved = False   # setup(sensitivity=True): the handle holds the sensitivities' workspace
         self._lu_stale = False        # update_affine since the last setup / update(l=, u=): QP.l / QP.u are not the solve's
 
     # ------------------------------------------------------------------ helpers
@@ -160,7 +165,8 @@ class ReLU_QP(object):
               polish=False,
               delta=1e-6,
               polish_refine_iter=3,
-              differentiable=False):
+              differentiable=False,
+              sensitivity=False):
         """
         Setup ReLU-QP solver problem of the form
 
@@ -199,7 +205,9 @@ class ReLU_QP(object):
         ``results.active`` holds the active set.  Reserved at setup: ``update_settings(polish=...)`` needs it.
         ``differentiable=True`` reserves the adjoint's workspace (C-ABI rqp_set_adjoint): ``adjoint()`` then differentiates
         the last solve (reluqp.layer wraps it as a torch.autograd.Function).  ``delta`` and ``polish_refine_iter`` set
-        both reduced-KKT solves: polish's and the adjoint's.
+        both reduced-KKT solves: polish's and the adjoint's.  ``sensitivity=True`` reserves the forward sensitivities'
+        workspace (C-ABI rqp_set_sensitivity): ``jvp()`` then pushes tangents of the data through the last solve (same
+        ``delta`` and ``polish_refine_iter``).
         """
         if devices is not None:
             from reluqp.multidevice import DeviceShards
@@ -213,7 +221,7 @@ class ReLU_QP(object):
                       check_infeasibility=check_infeasibility, eps_prim_inf=eps_prim_inf, eps_dual_inf=eps_dual_inf,
                       kernel=kernel, iterate_dtype=iterate_dtype, low_memory=low_memory, full_ladder=full_ladder,
                       graph_passes=graph_passes, polish=polish, delta=delta, polish_refine_iter=polish_refine_iter,
-                      differentiable=differentiable)
+                      differentiable=differentiable, sensitivity=sensitivity)
             self._shards = DeviceShards(ReLU_QP, list(devices), H, g, A, l, u, kw)
             first = self._shards.children[0]
             self.settings, self.QP, self.layers, self._rhos = first.settings, first.QP, first.layers, first._rhos
@@ -243,6 +251,7 @@ class ReLU_QP(object):
                                  polish_refine_iter=int(polish_refine_iter))
         self._polish_reserved = bool(polish)
         self._adj_reserved = bool(differentiable)
+        self._sens_reserved = bool(sensitivity)
         self._lu_stale = False
         if kernel not in _cabi.KERNELS:
             raise ValueError("kernel must be one of %s" % sorted(_cabi.KERNELS))
@@ -269,8 +278,11 @@ class ReLU_QP(object):
                 _cabi.check(h, lib.rqp_set_window_passes(h, int(graph_passes)), "rqp_set_window_passes")
             if polish:
                 _cabi.check(h, lib.rqp_set_polish(h, 1, float(delta), int(polish_refine_iter)), "rqp_set_polish")
-            if differentiable:
-                _cabi.check(h, lib.rqp_set_adjoint(h, 1, float(delta), int(polish_refine_iter)), "rqp_set_adjoint")
+            if differentiable or sensitivity:     # (enable 0: only delta and refine_iter, which the sensitivities use)
+                _cabi.check(h, lib.rqp_set_adjoint(h, int(bool(differentiable)), float(delta), int(polish_refine_iter)),
+                            "rqp_set_adjoint")
+            if sensitivity:
+                _cabi.check(h, lib.rqp_set_sensitivity(h, 1), "rqp_set_sensitivity")
             _cabi.check(h, lib.rqp_setup(h, _cabi.ptr(qp.H), _cabi.ptr(qp.g), _cabi.ptr(qp.A), _cabi.ptr(qp.l),
                                          _cabi.ptr(qp.u), self._stream()), "rqp_setup")
             cnt = ctypes.c_int32()
@@ -400,7 +412,7 @@ class ReLU_QP(object):
                 raise ValueError("Invalid setting: {}".format(key))
         cs = self._csettings()
         _cabi.check(self._h, _cabi.load().rqp_update_settings(self._h, ctypes.byref(cs)), "rqp_update_settings")
-        if pol and self._adj_reserved:              # (delta and polish_refine_iter set the adjoint's solve too)
+        if pol and (self._adj_reserved or self._sens_reserved):   # (delta and polish_refine_iter set those solves too)
             st = self.settings
             with torch.cuda.device(st.device):
                 _cabi.check(self._h, _cabi.load().rqp_set_adjoint(
@@ -604,6 +616,117 @@ class ReLU_QP(object):
         if qp.batched:
             return Gradients(out["dH"], out["dg"], out["dA"], out["dl"], out["du"], ast, ares, act)
         return Gradients(out["dH"], out["dg"], out["dA"], out["dl"], out["du"], int(ast[0]), float(ares[0]), act[0])
+
+    # ------------------------------------------------------------- sensitivities
+    def jvp(self, dH=None, dg=None, dA=None, dl=None, du=None, *, active=None):
+        """Forward-mode sensitivities of the last ``solve()`` (C-ABI rqp_sensitivity; DESIGN.md section 5 "Forward
+        sensitivities"): the tangents (dx, dy, dz) of the solution along tangents of the data, at ``self.QP.H / A / l / u``
+        and ``results.x / z / y`` with the solve's exit codes.  See ``jvp_at`` for the tangent shapes.  Needs
+        ``setup(sensitivity=True)``; refused after ``update_affine()`` (QP.l / QP.u are then stale) and on devices=[...]."""
+        self._need_setup()
+        if not self._sens_reserved:
+            raise RuntimeError("jvp() needs setup(..., sensitivity=True)")
+        if self._lu_stale:
+            raise RuntimeError("jvp(): update_affine() left QP.l / QP.u stale; call update(l=, u=) or setup() first")
+        res, qp = self.results, self.QP
+        if res.x is None:
+            raise RuntimeError("jvp(): call solve() first")
+        return self.jvp_at(qp.H, qp.A, qp.l, qp.u, res.x, res.z, res.y, dH=dH, dg=dg, dA=dA, dl=dl, du=du,
+                           status=res.info.status_code, active=active)
+
+    def jvp_at(self, H, A, l, u, x, z, y, dH=None, dg=None, dA=None, dl=None, du=None, *, status=None, active=None):
+        """``jvp()`` at explicit data of this handle's shapes (the caller's units; nothing of the handle's state is read).
+
+        A tangent has the shape of its problem tensor on a batched problem (one direction per instance), or that shape plus a
+        trailing ``ndir`` axis; without the batch axis (``[n]``, ``[n, ndir]``, ...) it is shared by every instance.  Every
+        tangent given must carry the same ``ndir``; None is zero.  Returns ``Sensitivities(dx, dy, dz, status, residual,
+        active)`` with dx [batch, n, ndir], dy / dz [batch, m, ndir] -- the ``ndir`` axis squeezed when no tangent had one
+        -- and per instance the status (1 computed, 0 not solved: zero tangents), the maximum relative residual over the
+        directions (NaN when skipped) and the active set.  ``status`` None treats every instance as solved."""
+        self._need_setup()
+        if not self._sens_reserved:
+            raise RuntimeError("jvp() needs setup(..., sensitivity=True)")
+        qp = self.QP
+        B, n, m = qp.batch, qp.nx, qp.nc
+        full = dict(dH=(B, n, n), dg=(B, n), dA=(B, m, n), dl=(B, m), du=(B, m))
+        tangents, ndir, squeeze = {}, None, True
+        for k, t in zip(_TANGENTS, (dH, dg, dA, dl, du)):
+            if t is None:
+                continue
+            t = _as_tensor(t)
+            shp, one = tuple(t.shape), full[k][1:]
+            if qp.batched and shp == full[k]:
+                t, sh, nd = t.unsqueeze(-1), False, 1
+            elif qp.batched and shp[:-1] == full[k] and len(shp) == len(full[k]) + 1:
+                sh, nd, squeeze = False, shp[-1], False
+            elif shp == one:
+                t, sh, nd = t.unsqueeze(-1), True, 1
+            elif shp[:-1] == one and len(shp) == len(one) + 1:
+                sh, nd, squeeze = True, shp[-1], False
+            else:
+                raise ValueError("%s has shape %s; expected %s or %s, with an optional trailing ndir axis"
+                                 % (k, shp, full[k] if qp.batched else one, one))
+            if ndir is not None and nd != ndir:
+                raise ValueError("every tangent must carry the same number of directions (%s has %d, not %d)" % (k, nd, ndir))
+            ndir = nd
+            tangents[k] = (t, sh)
+        if ndir is None:
+            ndir = 1
+        out = self._sens_call(H, A, l, u, x, z, y, tangents, ndir, status=status, active=active)
+        dx, dy, dz, sst, sres, act = out
+        if squeeze:
+            dx, dy, dz = dx.squeeze(-1), dy.squeeze(-1), dz.squeeze(-1)
+        if qp.batched:
+            return Sensitivities(dx, dy, dz, sst, sres, act)
+        return Sensitivities(dx[0], dy[0], dz[0], int(sst[0]), float(sres[0]), act[0])
+
+    def _sens_call(self, H, A, l, u, x, z, y, tangents, ndir, status=None, active=None, want_dz=True):
+        """rqp_sensitivity on device copies: ``tangents`` maps names of _TANGENTS to (tensor [.., ndir], shared).
+        Returns dx [B, n, ndir], dy / dz [B, m, ndir] (dz None without want_dz), status, residual, active."""
+        self._need_setup()
+        if not self._sens_reserved:
+            raise RuntimeError("jvp() needs setup(..., sensitivity=True)")
+        st, qp = self.settings, self.QP
+        B, n, m = qp.batch, qp.nx, qp.nc
+        lead = (B,) if qp.batched else ()
+        matlead = (B,) if (qp.batched and not qp.shared_mats) else ()
+        one = dict(dH=(n, n), dg=(n,), dA=(m, n), dl=(m,), du=(m,))
+        dev, prec = st.device, st.precision
+        with torch.cuda.device(dev):
+            H = self._to_dev(H, matlead + (n, n), "H")
+            A = self._to_dev(A, matlead + (m, n), "A")
+            x = self._to_dev(x, lead + (n,), "x")
+            y = self._to_dev(y, lead + (m,), "y")
+            l = None if l is None else self._to_dev(l, lead + (m,), "l")
+            u = None if u is None else self._to_dev(u, lead + (m,), "u")
+            z = None if z is None else self._to_dev(z, lead + (m,), "z")
+            if status is not None:
+                status = torch.as_tensor(status).to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+            if active is not None:
+                active = torch.as_tensor(active).to(device=dev, dtype=torch.int8).reshape(B, m).contiguous()
+            tan, bits = {}, 0
+            for k in _TANGENTS:
+                if k not in tangents:
+                    tan[k] = None
+                    continue
+                t, sh = tangents[k]
+                tan[k] = self._to_dev(t, (() if sh else (B,)) + one[k] + (ndir,), k)
+                if sh:
+                    bits |= _cabi.SENS_SHARED[k]
+            dx = torch.empty(B, n, ndir, device=dev, dtype=prec)
+            dy = torch.empty(B, m, ndir, device=dev, dtype=prec)
+            dz = torch.empty(B, m, ndir, device=dev, dtype=prec) if want_dz else None
+            act = torch.empty(B, m, device=dev, dtype=torch.int8)
+            sst = torch.empty(B, device=dev, dtype=torch.int32)
+            sres = torch.empty(B, device=dev, dtype=torch.float64)
+            ptrs = [None if t is None else t.data_ptr() for t in (H, A, l, u, x, z, y, status, active)]
+            outs = [None if t is None else t.data_ptr() for t in
+                    [tan[k] for k in _TANGENTS] + [dx, dy, dz, act, sst, sres]]
+            io = _cabi.SensitivityIO(*ptrs, int(ndir), bits, *outs)
+            _cabi.check(self._h, _cabi.load().rqp_sensitivity(self._h, ctypes.byref(io), self._stream()), "rqp_sensitivity")
+            if self.synchronous:
+                torch.cuda.current_stream(dev).synchronize()
+        return dx, dy, dz, sst, sres, act
 
     # --------------------------------------------------------------- warm start
     def warm_start(self, x=None, z=None, lam=None, rho=None):
