@@ -400,13 +400,55 @@ int rqp_set_sensitivity(rqp_handle* h, int32_t enable);
  * or was set up without rqp_set_sensitivity.                                                                            */
 int rqp_sensitivity(rqp_handle* h, const rqp_sensitivity_io* io, void* stream);
 
+/* ---- Condensing linear time-varying MPC problems on the device (DESIGN.md section 5 "LTV condensing") ----
+ * Per instance b and stage k = 0 .. horizon-1:  x_{k+1} = A_k x_k + B_k u_k + c_k,  u_k = -K x_k + v_k, box constraints
+ * l_add <= y <= u_add on y = [u_0, x_1, u_1, x_2, ..., u_{N-1}, x_N] (m = horizon (nu + nx)), decision variables
+ * v = [v_0 .. v_{N-1}] (n = horizon nu), weights H_sp = blkdiag(R, Q, ..., R, Qf).  With y = F v + G x0 + f:
+ *     H = sym(F' H_sp F),  A = F,  g = F' H_sp (G x0 + f - yref),  l / u = l_add / u_add - (G x0 + f),
+ * yref = [uref_0, xref_1, ...]; the first input is u_0 = v_0 - K x0.  These functions take no handle: they write plain
+ * row-major tensors in the layouts rqp_setup / rqp_update_mats / rqp_update read ([batch][n][n], [batch][m][n],
+ * [batch][n], [batch][m]), usable with any handle of dims (n, m, batch, shared_mats = 0, dtype).
+ * Batched inputs and all outputs are DEVICE arrays of dims.dtype; the shared weights Q [nx][nx], R [nu][nu], Qf [nx][nx]
+ * (symmetric) and K [nu][nx] are DEVICE arrays of double whatever dims.dtype.  Arithmetic is float64; every output is rounded
+ * once.  Everything is enqueued on `stream` of `device`: no host synchronisation, no allocation -- the float64 workspace
+ * (rqp_ltv_workspace_bytes) belongs to the caller and carries F, H_sp F, [G | f] and F' H_sp [G | f] from rqp_ltv_condense to
+ * any number of rqp_ltv_vectors calls.  Sizes: nx <= 16, nu <= 8, horizon <= 32, n <= 160, m <= 640, else
+ * RQP_ERR_UNSUPPORTED.  A failure's text: rqp_last_error(NULL) (per host thread, cleared at the entry of each rqp_ltv_* call).
+ * The calling thread's current HIP device is the same after the call as before it.                                           */
+#define RQP_LTV_HAS_K 1            /* K is given (else K = 0)                                              */
+#define RQP_LTV_HAS_C 2            /* c [batch][horizon][nx] is given (else c = 0)                         */
+#define RQP_LTV_HAS_XREF 4         /* rqp_ltv_vectors: xref [batch][horizon][nx] (x_1 .. x_N) is given     */
+#define RQP_LTV_HAS_UREF 8         /* rqp_ltv_vectors: uref [batch][horizon][nu] is given                  */
+#define RQP_LTV_BOUNDS_BATCHED 16  /* l_add, u_add are [batch][m] (else [m], shared)                       */
+typedef struct rqp_ltv_dims {
+    int32_t batch, nx, nu, horizon;
+    int32_t dtype;               /* rqp_dtype of the batched inputs and of every output                  */
+    int32_t flags;               /* RQP_LTV_* bits; a set bit makes its pointer mandatory                */
+} rqp_ltv_dims;
+
+/* Bytes of workspace rqp_ltv_condense / rqp_ltv_vectors need for these dims (the flags do not change it). */
+int rqp_ltv_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes);
+
+/* Transition + Hessian step: Ad [batch][horizon][nx][nx], Bd [batch][horizon][nx][nu] (and c, K by the flags) ->
+ * H [batch][n][n] (bitwise symmetric), A [batch][m][n] (= F; its structural zeros are exact), and the workspace.    */
+int rqp_ltv_condense(const rqp_ltv_dims* dims, int device, const void* Ad, const void* Bd, const void* c,
+                     const double* Q, const double* R, const double* Qf, const double* K,
+                     void* H, void* A, void* workspace, void* stream);
+
+/* Vector step from the workspace of the last rqp_ltv_condense with the same dims (its HAS_K / HAS_C flags included):
+ * x0 [batch][nx] (and xref, uref by the flags; l_add, u_add [m] or [batch][m]) -> g [batch][n], l, u [batch][m].      */
+int rqp_ltv_vectors(const rqp_ltv_dims* dims, int device, const void* x0, const void* xref, const void* uref,
+                    const void* l_add, const void* u_add, const double* Q, const double* R, const double* Qf,
+                    const void* workspace, void* g, void* l, void* u, void* stream);
+
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);
 
 int rqp_destroy(rqp_handle* h);
 
 const char* rqp_strerror(int err);
-/* Text of the last failure on this handle (HIP error string etc.).                */
+/* Text of the last failure on this handle (HIP error string etc.); h == NULL: of the last failed handle-less call
+ * (rqp_ltv_*) on this host thread.                                                                                */
 const char* rqp_last_error(const rqp_handle* h);
 /* Library / ABI version, e.g. "rqp-hip 0.1 gfx950".                               */
 const char* rqp_version(void);

@@ -1044,7 +1044,80 @@ const char* rqp_strerror(int err) {
     }
 }
 
-const char* rqp_last_error(const rqp_handle* h) { return h ? h->err.c_str() : ""; }
+// ---- LTV condensing: handle-less (the product is plain tensors); a failure's text is kept per host thread
+static thread_local std::string ltv_err;
+static int ltv_fail(int code, const std::string& what) {
+    ltv_err = what;
+    return code;
+}
+static int ltv_check(const rqp_ltv_dims* d, const char* fn) {
+    if (const char* w = rqp_ltv_check_dims(d)) return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": " + w);
+    if (const char* w = rqp_ltv_check_size(d)) return ltv_fail(RQP_ERR_UNSUPPORTED, std::string(fn) + ": " + w);
+    return RQP_OK;
+}
+// The launches run with `device` current; the calling thread's current device is put back afterwards (LtvDevice's destructor).
+struct LtvDevice {
+    int prev = -1;
+    int enter(int device, const char* fn) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+            return ltv_fail(RQP_ERR_HIP, std::string(fn) + ": no such HIP device");
+        int cur = 0;
+        hipError_t e = hipGetDevice(&cur);
+        if (e == hipSuccess && cur != device) {
+            e = hipSetDevice(device);
+            if (e == hipSuccess) prev = cur;
+        }
+        if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+        return RQP_OK;
+    }
+    ~LtvDevice() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+int rqp_ltv_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes) {
+    ltv_err.clear();
+    if (!bytes) return ltv_fail(RQP_ERR_ARG, "rqp_ltv_workspace_bytes: bytes is NULL");
+    if (int rc = ltv_check(dims, "rqp_ltv_workspace_bytes")) return rc;
+    *bytes = rqp_ltv_ws_bytes(dims);
+    return RQP_OK;
+}
+
+int rqp_ltv_condense(const rqp_ltv_dims* dims, int device, const void* Ad, const void* Bd, const void* c, const double* Q,
+                     const double* R, const double* Qf, const double* K, void* H, void* A, void* workspace, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_check(dims, "rqp_ltv_condense")) return rc;
+    if (!Ad || !Bd || !Q || !R || !Qf || !H || !A || !workspace)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense: Ad, Bd, Q, R, Qf, H, A and workspace are required");
+    if (((dims->flags & RQP_LTV_HAS_K) && !K) || ((dims->flags & RQP_LTV_HAS_C) && !c))
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense: a flag names an input whose pointer is NULL");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_condense")) return rc;
+    hipError_t e = rqp_ltv_launch_condense(dims, Ad, Bd, c, Q, R, Qf, K, H, A, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_condense: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+int rqp_ltv_vectors(const rqp_ltv_dims* dims, int device, const void* x0, const void* xref, const void* uref, const void* l_add,
+                    const void* u_add, const double* Q, const double* R, const double* Qf, const void* workspace, void* g, void* l,
+                    void* u, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_check(dims, "rqp_ltv_vectors")) return rc;
+    if (!x0 || !l_add || !u_add || !Q || !R || !Qf || !workspace || !g || !l || !u)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_vectors: x0, l_add, u_add, Q, R, Qf, workspace, g, l and u are required");
+    if (((dims->flags & RQP_LTV_HAS_XREF) && !xref) || ((dims->flags & RQP_LTV_HAS_UREF) && !uref))
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_vectors: a flag names an input whose pointer is NULL");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_vectors")) return rc;
+    hipError_t e = rqp_ltv_launch_vectors(dims, x0, (dims->flags & RQP_LTV_HAS_XREF) ? xref : nullptr,
+                                          (dims->flags & RQP_LTV_HAS_UREF) ? uref : nullptr, l_add, u_add, Q, R, Qf, workspace, g, l,
+                                          u, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_vectors: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+const char* rqp_last_error(const rqp_handle* h) { return h ? h->err.c_str() : ltv_err.c_str(); }
 
 const char* rqp_version(void) { return RQP_VERSION; }
 

@@ -311,3 +311,13 @@ hipError_t rqp_launch_solve_mfma16(const rqp_handle* h, const SolveArgs& a, hipS
 hipError_t rqp_raise_lds_limit(const void* fn, size_t bytes);
 
 static inline int rqp_round_up(int v, int q) { return (v + q - 1) / q * q; }
+
+// LTV condensing (rqp_condense.hip): handle-less; the check functions return NULL or the message of the failure
+const char* rqp_ltv_check_dims(const rqp_ltv_dims* d);       // RQP_ERR_ARG
+const char* rqp_ltv_check_size(const rqp_ltv_dims* d);       // RQP_ERR_UNSUPPORTED
+size_t rqp_ltv_ws_bytes(const rqp_ltv_dims* d);
+hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
+                                   const double* R, const double* Qf, const double* K, void* H, void* A, void* ws, hipStream_t s);
+hipError_t rqp_ltv_launch_vectors(const rqp_ltv_dims* d, const void* x0, const void* xref, const void* uref, const void* l_add,
+                                  const void* u_add, const double* Q, const double* R, const double* Qf, const void* ws, void* g,
+                                  void* l, void* u, hipStream_t s);

@@ -24,7 +24,8 @@ ABI_SYMBOLS = (
     "rqp_default_settings", "rqp_create", "rqp_setup", "rqp_update", "rqp_update_mats", "rqp_update_affine",
     "rqp_update_settings",
     "rqp_warm_start", "rqp_clear_primal_dual", "rqp_solve", "rqp_iterate", "rqp_compute_residuals",
-    "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
+    "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity",
+    "rqp_ltv_workspace_bytes", "rqp_ltv_condense", "rqp_ltv_vectors", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
     "rqp_last_error", "rqp_version",
 )
 
@@ -69,6 +70,14 @@ class SensitivityIO(ctypes.Structure):
                 [("ndir", ctypes.c_int32), ("shared_tangents", ctypes.c_int32)] +
                 [(f, ctypes.c_void_p) for f in ("dH", "dg", "dA", "dl", "du", "dx", "dy", "dz", "active_out", "sens_status",
                                                 "sens_res")])
+
+
+LTV_HAS_K, LTV_HAS_C, LTV_HAS_XREF, LTV_HAS_UREF, LTV_BOUNDS_BATCHED = 1, 2, 4, 8, 16     # RQP_LTV_* (rqp_ltv_dims.flags)
+
+
+class LtvDims(ctypes.Structure):
+    """struct rqp_ltv_dims."""
+    _fields_ = [(f, ctypes.c_int32) for f in ("batch", "nx", "nu", "horizon", "dtype", "flags")]
 
 
 class CInfo(ctypes.Structure):
@@ -126,6 +135,9 @@ def load():
         "rqp_adjoint": (ctypes.c_int, [H, ctypes.POINTER(AdjointIO), vp]),
         "rqp_set_sensitivity": (ctypes.c_int, [H, i32]),
         "rqp_sensitivity": (ctypes.c_int, [H, ctypes.POINTER(SensitivityIO), vp]),
+        "rqp_ltv_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.POINTER(ctypes.c_size_t)]),
+        "rqp_ltv_condense": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 11),
+        "rqp_ltv_vectors": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 13),
         "rqp_kernel_name": (ctypes.c_char_p, [H]),
         "rqp_destroy": (ctypes.c_int, [H]),
         "rqp_strerror": (ctypes.c_char_p, [ctypes.c_int]),
@@ -140,12 +152,13 @@ def load():
     return lib
 
 
-def check(handle, rc, what):
+def check(handle, rc, what, handleless=False):
+    """``handleless=True`` (the rqp_ltv_* calls): the detail is the thread's last handle-less failure, rqp_last_error(NULL)."""
     if rc == 0:
         return
     lib = load()
     msg = lib.rqp_strerror(rc).decode()
-    detail = lib.rqp_last_error(handle).decode() if handle else ""
+    detail = lib.rqp_last_error(handle).decode() if (handle or handleless) else ""
     err = RqpError("%s failed: %s (%d)%s" % (what, msg, rc, (": " + detail) if detail else ""))
     err.code = rc
     raise err

@@ -315,3 +315,381 @@ class LinearMPC(object):
             it = res.info.iter
             its.append(it.cpu().numpy() if hasattr(it, "cpu") else np.atleast_1d(np.asarray(it)))
         return np.stack(xs), np.stack(us), np.stack(its)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Linear time-varying (LTV) plants, one linearisation per instance: x_{k+1} = A_k x_k + B_k u_k + c_k, u_k = -K x_k + v_k.
+# y = [u_0, x_1, ..., u_{N-1}, x_N] = F v + G x0 + f;  H = sym(F'H_sp F), A = F (box constraints: A_add = I),
+# g = F'H_sp (G x0 + f - yref), l / u = l_add / u_add - (G x0 + f), first input u_0 = v_0 - K x0.
+# condense_ltv is the host statement of these formulas (dense F, G, then F.T @ H_sp @ F); condense_ltv_device /
+# ltv_vectors_device run them on the device (C-ABI rqp_ltv_condense / rqp_ltv_vectors) straight into the tensors
+# setup() / update() read, and BatchedLTVMPC is the closed-loop driver on top.
+
+LTV_LIMITS = dict(nx=16, nu=8, horizon=32, n=160, m=640)     # what the device kernels hold (rqp_abi.h)
+
+
+def _ltv_shapes(Ad, Bd):
+    if Ad.ndim != 4 or Bd.ndim != 4:
+        raise ValueError("Ad must be [B, N, nx, nx] and Bd [B, N, nx, nu], got %s and %s" % (tuple(Ad.shape), tuple(Bd.shape)))
+    B, N, nx, nu = Ad.shape[0], Ad.shape[1], Ad.shape[2], Bd.shape[3]
+    if tuple(Ad.shape) != (B, N, nx, nx) or tuple(Bd.shape) != (B, N, nx, nu):
+        raise ValueError("Ad must be [B, N, nx, nx] and Bd [B, N, nx, nu], got %s and %s" % (tuple(Ad.shape), tuple(Bd.shape)))
+    return B, N, nx, nu
+
+
+def _ltv_check_sizes(nx, nu, N):
+    L = LTV_LIMITS
+    if nx < 1 or nu < 1 or N < 1:
+        raise ValueError("nx, nu and horizon must be >= 1")
+    if nx > L["nx"] or nu > L["nu"] or N > L["horizon"] or N * nu > L["n"] or N * (nx + nu) > L["m"]:
+        raise ValueError("unsupported LTV size (nx=%d, nu=%d, horizon=%d): the device condensing holds nx <= %d, nu <= %d, "
+                         "horizon <= %d, n = horizon nu <= %d, m = horizon (nx + nu) <= %d"
+                         % (nx, nu, N, L["nx"], L["nu"], L["horizon"], L["n"], L["m"]))
+
+
+def _ltv_weights(nx, nu, Q, R, Qf, K):
+    Q, R, Qf = (np.asarray(a, dtype=np.float64) for a in (Q, R, Qf))
+    if Q.shape != (nx, nx) or Qf.shape != (nx, nx) or R.shape != (nu, nu):
+        raise ValueError("Q, Qf must be [%d, %d] and R [%d, %d]" % (nx, nx, nu, nu))
+    for name, W in (("Q", Q), ("R", R), ("Qf", Qf)):                # symmetric up to rounding (a Riccati P is): the symmetric part is used
+        if np.abs(W - W.T).max() > 1e-9 * max(np.abs(W).max(), 1e-300):
+            raise ValueError("%s must be symmetric" % name)
+    Q, R, Qf = (0.5 * (W + W.T) for W in (Q, R, Qf))
+    if K is not None:
+        K = np.asarray(K, dtype=np.float64)
+        if K.shape != (nu, nx):
+            raise ValueError("K has shape %s, expected (%d, %d)" % (K.shape, nu, nx))
+    return Q, R, Qf, K
+
+
+def condense_ltv(Ad, Bd, Q, R, Qf, K=None, c=None):
+    """Condensed QP maps of LTV plants on the host (numpy, the formulas as written above).
+
+    Ad [N, nx, nx], Bd [N, nx, nu], c [N, nx] (optional) for one instance, or with a leading batch axis.  Returns a dict of
+    F [m, n], G [m, nx], f [m], H = sym(F'H_sp F) [n, n], A = F, g_x0 = F'H_sp G [n, nx], g_f = F'H_sp f [n], H_sp [m, m]
+    (each with the batch axis when the input has one; H_sp is shared).  Then for an initial state x0 and references:
+    g = g_x0 x0 + g_f - F'H_sp yref, l / u = l_add / u_add - (G x0 + f)  (``ltv_vectors``)."""
+    Ad, Bd = np.asarray(Ad), np.asarray(Bd)
+    if Ad.ndim == 4:
+        outs = [condense_ltv(Ad[b], Bd[b], Q, R, Qf, K=K, c=None if c is None else np.asarray(c)[b]) for b in range(Ad.shape[0])]
+        res = {k: np.stack([o[k] for o in outs]) for k in outs[0] if k != "H_sp"}
+        res["H_sp"] = outs[0]["H_sp"]
+        return res
+    dt = np.result_type(Ad.dtype, np.float64)                  # float64, or wider when the caller passes longdouble
+    Ad, Bd = Ad.astype(dt), Bd.astype(dt)
+    N, nx, nu = Ad.shape[0], Ad.shape[1], Bd.shape[2]
+    Q, R, Qf = (np.asarray(a).astype(dt) for a in (Q, R, Qf))
+    K = np.zeros((nu, nx), dtype=dt) if K is None else np.asarray(K).astype(dt)
+    c = np.zeros((N, nx), dtype=dt) if c is None else np.asarray(c).astype(dt)
+    Acl = [Ad[k] - Bd[k] @ K for k in range(N)]
+
+    memo = {}
+
+    def phi(k, j):                                             # Acl_{k-1} ... Acl_j, phi(j, j) = I (each product formed once)
+        if k == j:
+            return np.eye(nx, dtype=dt)
+        if (k, j) not in memo:
+            memo[(k, j)] = Acl[k - 1] @ phi(k - 1, j)
+        return memo[(k, j)]
+
+    blk = nu + nx
+    m, n = N * blk, N * nu
+    F, G, f = np.zeros((m, n), dtype=dt), np.zeros((m, nx), dtype=dt), np.zeros(m, dtype=dt)
+    xF, xG, xf = np.zeros((N + 1, nx, n), dtype=dt), np.zeros((N + 1, nx, nx), dtype=dt), np.zeros((N + 1, nx), dtype=dt)
+    for k in range(N + 1):                                     # x_k = phi(k, 0) x0 + sum_{j<k} phi(k, j+1) (B_j v_j + c_j)
+        xG[k] = phi(k, 0)
+        for j in range(k):
+            P = phi(k, j + 1)
+            xF[k][:, j * nu:(j + 1) * nu] = P @ Bd[j]
+            xf[k] += P @ c[j]
+    for k in range(N):                                         # u_k = -K x_k + v_k
+        ru, rx = slice(k * blk, k * blk + nu), slice(k * blk + nu, (k + 1) * blk)
+        F[ru] = -K @ xF[k]
+        F[ru, k * nu:(k + 1) * nu] += np.eye(nu, dtype=dt)
+        G[ru], f[ru] = -K @ xG[k], -K @ xf[k]
+        F[rx], G[rx], f[rx] = xF[k + 1], xG[k + 1], xf[k + 1]
+    H_sp = np.zeros((m, m), dtype=dt)
+    for k in range(N):
+        H_sp[k * blk:k * blk + nu, k * blk:k * blk + nu] = R
+        H_sp[k * blk + nu:(k + 1) * blk, k * blk + nu:(k + 1) * blk] = Qf if k == N - 1 else Q
+    H = F.T @ H_sp @ F
+    H = (H + H.T) / 2
+    return dict(F=F, G=G, f=f, H=H, A=F, g_x0=F.T @ H_sp @ G, g_f=F.T @ H_sp @ f, H_sp=H_sp)
+
+
+def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None):
+    """(g, l, u) of the condensed LTV QP from ``condense_ltv``'s maps (one instance: x0 [nx]; batch: x0 [B, nx])."""
+    F, G, f = cond["F"], cond["G"], cond["f"]
+    x0 = np.asarray(x0, dtype=F.dtype)
+    if F.ndim == 3:
+        outs = [ltv_vectors({k: (v if k == "H_sp" else v[b]) for k, v in cond.items()}, x0[b],
+                            np.asarray(l_add)[b] if np.ndim(l_add) == 2 else l_add,
+                            np.asarray(u_add)[b] if np.ndim(u_add) == 2 else u_add,
+                            None if xref is None else xref[b], None if uref is None else uref[b]) for b in range(F.shape[0])]
+        return tuple(np.stack([o[i] for o in outs]) for i in range(3))
+    m, nx = G.shape
+    s = G @ x0 + f
+    g = cond["g_x0"] @ x0 + cond["g_f"]
+    if xref is not None or uref is not None:
+        n = F.shape[1]
+        # (N, nu) from the shapes: m = N (nu + nx), n = N nu
+        N = (m - n) // nx
+        nu = n // N
+        yref = np.zeros((N, nu + nx), dtype=F.dtype)
+        if uref is not None:
+            yref[:, :nu] = uref
+        if xref is not None:
+            yref[:, nu:] = xref
+        g = g - F.T @ (cond["H_sp"] @ yref.reshape(-1))
+    return g, np.asarray(l_add, dtype=F.dtype) - s, np.asarray(u_add, dtype=F.dtype) - s
+
+
+class _LtvWeights(object):
+    """Q, R, Qf (and K) as float64 device tensors (what the C-ABI reads), cached per device."""
+
+    def __init__(self, nx, nu, Q, R, Qf, K):
+        self.Q, self.R, self.Qf, self.K = _ltv_weights(nx, nu, Q, R, Qf, K)
+        self._dev = {}
+
+    def on(self, device):
+        import torch
+        key = str(device)
+        if key not in self._dev:
+            t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=device)
+            self._dev[key] = tuple(t(a) for a in (self.Q, self.R, self.Qf, self.K))
+        return self._dev[key]
+
+
+def ltv_workspace(batch, nx, nu, horizon, device):
+    """The float64 workspace of ``condense_ltv_device`` / ``ltv_vectors_device`` for these sizes (a device tensor)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    _ltv_check_sizes(nx, nu, horizon)
+    lib = _cabi.load()
+    dims = _cabi.LtvDims(batch=batch, nx=nx, nu=nu, horizon=horizon, dtype=_cabi.RQP_F64, flags=0)
+    nbytes = ctypes.c_size_t()
+    _cabi.check(None, lib.rqp_ltv_workspace_bytes(ctypes.byref(dims), ctypes.byref(nbytes)), "rqp_ltv_workspace_bytes", handleless=True)
+    return torch.empty(nbytes.value // 8, dtype=torch.float64, device=device)
+
+
+def _ltv_out(t, shape, dtype, device, name):
+    import torch
+    if t is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(t.shape) != tuple(shape) or t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, tuple(shape), device))
+    return t
+
+
+def _ltv_in(t, shape, dtype, device, name):
+    import torch
+    t = torch.as_tensor(t).to(device=device, dtype=dtype).contiguous()
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+    return t
+
+
+def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
+    """H [B, n, n], A [B, m, n] of the condensed LTV QPs, built on the device (C-ABI rqp_ltv_condense) from device tensors
+    Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]) of the output precision (float32 or float64).  ``weights`` is
+    ``(Q, R, Qf, K)`` (numpy, K may be None) or an ``_LtvWeights``; ``workspace`` from ``ltv_workspace`` carries the maps the
+    vector step needs.  ``H`` / ``A``: optional output tensors.  Enqueued on the current stream; returns (H, A)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    B, N, nx, nu = _ltv_shapes(Ad, Bd)
+    _ltv_check_sizes(nx, nu, N)
+    if not torch.is_tensor(Ad) or Ad.device.type != "cuda":
+        raise _cabi.RqpUnavailable("condense_ltv_device needs device tensors; the host restatement is condense_ltv")
+    dtype, device = Ad.dtype, Ad.device
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("Ad must be float32 or float64")
+    w = weights if isinstance(weights, _LtvWeights) else _LtvWeights(nx, nu, *weights)
+    Q, R, Qf, K = w.on(device)
+    n, m = N * nu, N * (nx + nu)
+    Ad, Bd = _ltv_in(Ad, (B, N, nx, nx), dtype, device, "Ad"), _ltv_in(Bd, (B, N, nx, nu), dtype, device, "Bd")
+    c = None if c is None else _ltv_in(c, (B, N, nx), dtype, device, "c")
+    H, A = _ltv_out(H, (B, n, n), dtype, device, "H"), _ltv_out(A, (B, m, n), dtype, device, "A")
+    flags = (_cabi.LTV_HAS_K if K is not None else 0) | (_cabi.LTV_HAS_C if c is not None else 0)
+    dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
+                         flags=flags)
+    lib = _cabi.load()
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_condense(ctypes.byref(dims), device.index or 0, _cabi.ptr(Ad), _cabi.ptr(Bd), _cabi.ptr(c),
+                                               _cabi.ptr(Q), _cabi.ptr(R), _cabi.ptr(Qf), _cabi.ptr(K), _cabi.ptr(H), _cabi.ptr(A),
+                                               _cabi.ptr(workspace), stream), "rqp_ltv_condense", handleless=True)
+    return H, A
+
+
+def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, uref=None, g=None, l=None, u=None):
+    """g [B, n], l, u [B, m] from the workspace of the last ``condense_ltv_device`` (C-ABI rqp_ltv_vectors).
+    ``dims5`` = (nx, nu, horizon, has_K, has_c) of that call; x0 [B, nx] (xref [B, N, nx], uref [B, N, nu]) device tensors of the
+    output precision, l_add / u_add [m] or [B, m].  Enqueued on the current stream; returns (g, l, u)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    nx, nu, N, has_K, has_c = dims5
+    if not torch.is_tensor(x0) or x0.device.type != "cuda":
+        raise _cabi.RqpUnavailable("ltv_vectors_device needs device tensors; the host restatement is ltv_vectors")
+    dtype, device, B = x0.dtype, x0.device, x0.shape[0]
+    n, m = N * nu, N * (nx + nu)
+    x0 = _ltv_in(x0, (B, nx), dtype, device, "x0")
+    xref = None if xref is None else _ltv_in(xref, (B, N, nx), dtype, device, "xref")
+    uref = None if uref is None else _ltv_in(uref, (B, N, nu), dtype, device, "uref")
+    batched = torch.as_tensor(l_add).dim() == 2
+    l_add = _ltv_in(l_add, (B, m) if batched else (m,), dtype, device, "l_add")
+    u_add = _ltv_in(u_add, (B, m) if batched else (m,), dtype, device, "u_add")
+    w = weights if isinstance(weights, _LtvWeights) else _LtvWeights(nx, nu, *weights)
+    Q, R, Qf, _ = w.on(device)
+    g, l, u = (_ltv_out(g, (B, n), dtype, device, "g"), _ltv_out(l, (B, m), dtype, device, "l"),
+               _ltv_out(u, (B, m), dtype, device, "u"))
+    flags = ((_cabi.LTV_HAS_K if has_K else 0) | (_cabi.LTV_HAS_C if has_c else 0) | (_cabi.LTV_HAS_XREF if xref is not None else 0)
+             | (_cabi.LTV_HAS_UREF if uref is not None else 0) | (_cabi.LTV_BOUNDS_BATCHED if batched else 0))
+    dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
+                         flags=flags)
+    lib = _cabi.load()
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_vectors(ctypes.byref(dims), device.index or 0, _cabi.ptr(x0), _cabi.ptr(xref), _cabi.ptr(uref),
+                                              _cabi.ptr(l_add), _cabi.ptr(u_add), _cabi.ptr(Q), _cabi.ptr(R), _cabi.ptr(Qf),
+                                              _cabi.ptr(workspace), _cabi.ptr(g), _cabi.ptr(l), _cabi.ptr(u), stream),
+                    "rqp_ltv_vectors", handleless=True)
+    return g, l, u
+
+
+class BatchedLTVMPC(object):
+    """Closed-loop MPC on a batch of plants that each have their own, time-varying linearisation.
+
+    ``linearize(Ad, Bd, c=None)`` condenses the batch on the device (first call: ``ReLU_QP.setup`` with per-instance
+    matrices; later calls: ``update(Hx=, Ax=)``, which re-factors on the device and keeps the ADMM state), ``step(x)`` builds
+    (g, l, u) for the current states on the device, ``update(g, l, u)``, warm-started ``solve()``, and returns the first input
+    u_0 = v_0 - K x [B, nu] (a device tensor) and the ``Results``.  Weights Q, R, Qf and the pre-stabilising gain K are shared
+    by the batch; the box |u| <= u_max, |x| <= x_max is ``box_constraints``.  Only the solver's public setup / update /
+    solve are called, so every solver option (``precision``, ``polish``, ``sensitivity``, ``devices`` ...) works unchanged."""
+
+    def __init__(self, nx, nu, horizon, Q, R, Qf, u_max, x_max, K=None, solver=None, **solver_kw):
+        nx, nu, horizon = int(nx), int(nu), int(horizon)
+        _ltv_check_sizes(nx, nu, horizon)
+        self.nx, self.nu, self.horizon = nx, nu, horizon
+        self.n, self.m = horizon * nu, horizon * (nx + nu)
+        self.weights = _LtvWeights(nx, nu, Q, R, Qf, K)
+        self.K = self.weights.K
+        _, l_add, u_add = box_constraints(nx, nu, horizon, u_max, x_max)
+        self.l_add, self.u_add = l_add, u_add
+        self.solver, self.solver_kw = solver, dict(solver_kw)
+        self._ready = False
+        self._lin = None                       # (has_c,) of the current linearisation
+        self._buf = None
+
+    def _place(self):
+        """(device, dtype) of the tensors the driver builds: the solver's device / precision options."""
+        import torch
+        kw = self.solver_kw
+        dtype = kw.get("precision", torch.float64)
+        if kw.get("devices"):
+            d = kw["devices"][0]
+            device = d if isinstance(d, torch.device) else torch.device("cuda", int(d))
+        else:
+            device = torch.device(kw.get("device", "cuda:0"))
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device, dtype
+
+    def _buffers(self, B, device, dtype):
+        import torch
+        if self._buf is None or self._buf["B"] != B:
+            e = lambda *s: torch.empty(s, dtype=dtype, device=device)
+            self._buf = dict(B=B, ws=ltv_workspace(B, self.nx, self.nu, self.horizon, device), H=e(B, self.n, self.n),
+                             A=e(B, self.m, self.n), g=e(B, self.n), l=e(B, self.m), u=e(B, self.m),
+                             l_add=torch.as_tensor(self.l_add, dtype=dtype, device=device),
+                             u_add=torch.as_tensor(self.u_add, dtype=dtype, device=device),
+                             Kt=None if self.K is None else torch.as_tensor(self.K.T.copy(), dtype=dtype, device=device))
+        return self._buf
+
+    def _handover(self, device):
+        """devices=[...]: the shards run on their own streams, so what this stream built must be complete first."""
+        import torch
+        if self.solver_kw.get("devices"):
+            torch.cuda.current_stream(device).synchronize()
+
+    def linearize(self, Ad, Bd, c=None):
+        """New stage matrices Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]): H and A of every instance are rebuilt on the
+        device; the solver is set up on the first ``step`` (it needs g, l, u) and re-factored, state kept, afterwards."""
+        import torch
+        from reluqp import _cabi
+        B, N, nx, nu = _ltv_shapes(Ad, Bd)
+        if (N, nx, nu) != (self.horizon, self.nx, self.nu):
+            raise ValueError("stages of shape (N=%d, nx=%d, nu=%d), expected (%d, %d, %d)" % (N, nx, nu, self.horizon, self.nx, self.nu))
+        if c is not None and tuple(c.shape) != (B, N, nx):
+            raise ValueError("c has shape %s, expected %s" % (tuple(c.shape), (B, N, nx)))
+        if not torch.cuda.is_available():
+            raise _cabi.RqpUnavailable("BatchedLTVMPC needs a HIP device; the MI355X build has no CPU path")
+        device, dtype = self._place()
+        buf = self._buffers(B, device, dtype)
+        to = lambda t: torch.as_tensor(t).to(device=device, dtype=dtype)
+        condense_ltv_device(to(Ad), to(Bd), self.weights, buf["ws"], c=None if c is None else to(c), H=buf["H"], A=buf["A"])
+        self._lin = (c is not None,)
+        if self._ready:
+            self._handover(device)
+            self.solver.update(Hx=buf["H"], Ax=buf["A"])
+        return None
+
+    def qp_vectors(self, x, xref=None, uref=None):
+        """(g, l, u) device tensors of the QPs for the states x [B, nx] under the current linearisation."""
+        import torch
+        if self._lin is None:
+            raise RuntimeError("BatchedLTVMPC: linearize() first")
+        device, dtype = self._place()
+        buf = self._buf
+        to = lambda t: None if t is None else torch.as_tensor(t).to(device=device, dtype=dtype)
+        x = to(x)
+        if tuple(x.shape) != (buf["B"], self.nx):
+            raise ValueError("x has shape %s, expected %s" % (tuple(x.shape), (buf["B"], self.nx)))
+        return ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
+                                  buf["u_add"], self.weights, buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"], l=buf["l"],
+                                  u=buf["u"])
+
+    def step(self, x, xref=None, uref=None):
+        """One control step for the states x [B, nx] (references xref [B, N, nx] for x_1 .. x_N, uref [B, N, nu]):
+        returns (u_0 [B, nu] device tensor, Results)."""
+        import torch
+        g, l, u = self.qp_vectors(x, xref, uref)
+        device, dtype = self._place()
+        buf = self._buf
+        self._handover(device)
+        if not self._ready:
+            import reluqp.reluqpth as reluqpth
+            self.solver = self.solver or reluqpth.ReLU_QP()
+            kw = dict(self.solver_kw)
+            if not kw.get("devices"):
+                kw["device"] = device
+            self.solver.setup(buf["H"], g, buf["A"], l, u, **kw)
+            self._ready = True
+        else:
+            self.solver.update(g=g, l=l, u=u)
+        res = self.solver.solve()
+        v0 = res.x[:, :self.nu].to(device)
+        x = torch.as_tensor(x).to(device=device, dtype=dtype)
+        u0 = v0.clone() if buf["Kt"] is None else v0 - x @ buf["Kt"]      # (never a view of the solver's result buffer)
+        return u0, res
+
+    def simulate(self, x0, steps, plant, relinearize_every=1, xref=None, uref=None):
+        """Closed loop on the device: ``plant(x, u) -> (x_next, Ad, Bd, c)`` is a torch callable returning the next states and
+        the linearisation to use from them (Ad [B, N, nx, nx], Bd [B, N, nx, nu], c [B, N, nx] or None).  The linearisation
+        is refreshed every ``relinearize_every`` steps; ``linearize()`` must have been called for the first one.
+        Returns (states [steps + 1, B, nx], inputs [steps, B, nu], iterations [steps, B]) as device tensors."""
+        import torch
+        device, dtype = self._place()
+        x = torch.as_tensor(x0).to(device=device, dtype=dtype)
+        xs, us, its = [x], [], []
+        for k in range(steps):
+            u0, res = self.step(x, xref=xref, uref=uref)
+            x, Ad, Bd, c = plant(x, u0)
+            if (k + 1) % relinearize_every == 0 and k + 1 < steps:
+                self.linearize(Ad, Bd, c)
+            xs.append(x)
+            us.append(u0)
+            its.append(res.info.iter.to(device).clone())
+        return torch.stack(xs), torch.stack(us), torch.stack(its)

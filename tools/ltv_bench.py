@@ -1,0 +1,123 @@
+"""Cost of condensing a batch of LTV plants on the device (reluqp.mpc.condense_ltv_device / ltv_vectors_device,
+include/rqp_abi.h rqp_ltv_condense / rqp_ltv_vectors) next to the solver calls it feeds.
+
+At B = 4096, (nx, nu, N) = (12, 4, 20) -> (n, m) = (80, 320), float32 and float64 outputs: device time (HIP events, median of
+--reps calls after warm-up) of `condense` (transition + Hessian kernels) and `vectors`, and of update(Hx, Ax) and a
+warm-started solve() of the handle set up on that data, in the same run.  The host path it replaces -- numpy condense_ltv
+over the batch on --workers processes plus the host-to-device copy of (H, A) -- is timed on --host-batch instances and
+scaled to B.  Per-kernel times: run the same command under `rocprofv3 --kernel-trace --stats`.
+
+    python tools/ltv_bench.py [--reps 20] [--out profiles/r8_ltv/ltv_bench.json]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from concurrent.futures import ProcessPoolExecutor
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [REPO, os.path.join(REPO, "reluqp-py_amd")]
+
+from reluqp import mpc  # noqa: E402
+
+NX, NU, N = 12, 4, 20
+
+
+def _host_one(args):
+    Ad, Bd, Q, R, P, K = args
+    c = mpc.condense_ltv(Ad, Bd, Q, R, P, K=K)
+    return c["H"], c["A"]
+
+
+def _host_baseline(Ad, Bd, Q, R, P, K, workers):
+    """Seconds per instance of the numpy path on `workers` processes (run before this process touches the GPU)."""
+    jobs = [(Ad[b], Bd[b], Q, R, P, K) for b in range(Ad.shape[0])]
+    with ProcessPoolExecutor(max_workers=workers) as pool:
+        list(pool.map(_host_one, jobs[:workers]))                 # start the workers
+        t0 = time.perf_counter()
+        out = list(pool.map(_host_one, jobs, chunksize=max(1, len(jobs) // (4 * workers))))
+        dt = time.perf_counter() - t0
+    return dt / len(jobs), out
+
+
+def _timed(torch, fn, reps, warm=3):
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    out = []
+    for _ in range(warm + reps):
+        ev[0].record()
+        fn()
+        ev[1].record()
+        ev[1].synchronize()
+        out.append(ev[0].elapsed_time(ev[1]))
+    return float(np.median(out[warm:])), float(np.min(out[warm:])), float(np.max(out[warm:]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4096)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--host-batch", type=int, default=256)
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r8_ltv", "ltv_bench.json"))
+    args = ap.parse_args()
+    B = args.batch
+    Ad0, Bd0 = mpc.random_plant(NX, NU, seed=0)
+    Q, R = np.eye(NX), 0.1 * np.eye(NU)
+    K, P = mpc.ihlqr(Ad0, Bd0, Q, R, Q)
+    rs = np.random.RandomState(1)
+    Ad = Ad0[None, None] + 0.02 * rs.randn(B, N, NX, NX) / np.sqrt(NX)
+    Bd = Bd0[None, None] + 0.02 * rs.randn(B, N, NX, NU)
+    x0 = 1.5 * rs.randn(B, NX)
+    hb = min(B, args.host_batch)
+    host_s, host_out = _host_baseline(Ad[:hb], Bd[:hb], Q, R, P, K, args.workers)
+
+    import torch
+    dev = torch.device("cuda:0")
+    res = []
+    for prec in (torch.float32, torch.float64):
+        t = lambda a: torch.as_tensor(a, device=dev, dtype=prec)
+        ctl = mpc.BatchedLTVMPC(NX, NU, N, Q, R, P, u_max=0.4, x_max=8.0, K=K, device=dev, precision=prec, eps_abs=1e-3)
+        Adt, Bdt, xt = t(Ad), t(Bd), t(x0)
+        ctl.linearize(Adt, Bdt)
+        ctl.step(xt)
+        buf, s = ctl._buf, ctl.solver
+        out = dict(batch=B, nx=NX, nu=NU, horizon=N, n=ctl.n, m=ctl.m, dtype=str(prec).replace("torch.", ""), kernel=s.kernel,
+                   reps=args.reps)
+        cond = lambda: mpc.condense_ltv_device(Adt, Bdt, ctl.weights, buf["ws"], H=buf["H"], A=buf["A"])
+        out["condense_ms"], out["condense_min_ms"], out["condense_max_ms"] = _timed(torch, cond, args.reps)
+        out["vectors_ms"], _, _ = _timed(torch, lambda: ctl.qp_vectors(xt), args.reps)
+        xr = t(0.1 * rs.randn(B, N, NX))
+        out["vectors_with_xref_ms"], _, _ = _timed(torch, lambda: ctl.qp_vectors(xt, xref=xr), args.reps)
+        ctl.qp_vectors(xt)
+        s.synchronous = False
+        out["update_mats_ms"], out["update_mats_min_ms"], out["update_mats_max_ms"] = _timed(
+            torch, lambda: s.update(Hx=buf["H"], Ax=buf["A"]), args.reps)
+
+        def warm_solve():
+            s.update(g=buf["g"], l=buf["l"], u=buf["u"])
+            s.solve()
+        out["warm_solve_ms"], _, _ = _timed(torch, warm_solve, args.reps)
+        torch.cuda.synchronize()
+        out["condense_over_update_mats"] = out["condense_ms"] / out["update_mats_ms"]
+        # the host path: numpy over the batch (scaled from --host-batch instances) + the copy of its (H, A) to the device
+        Hh = torch.as_tensor(np.stack([o[0] for o in host_out])).to(prec).pin_memory()
+        Ah = torch.as_tensor(np.stack([o[1] for o in host_out])).to(prec).pin_memory()
+        h2d, _, _ = _timed(torch, lambda: (Hh.to(dev, non_blocking=True), Ah.to(dev, non_blocking=True)), 5)
+        out["host_numpy_ms"] = host_s * B * 1e3
+        out["host_h2d_ms"] = h2d * B / hb
+        out["host_workers"], out["host_batch_timed"] = args.workers, hb
+        out["host_over_condense"] = (out["host_numpy_ms"] + out["host_h2d_ms"]) / out["condense_ms"]
+        print(json.dumps(out), flush=True)
+        res.append(out)
+        del ctl, s, buf
+        torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), results=res), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
