@@ -441,6 +441,40 @@ int rqp_ltv_vectors(const rqp_ltv_dims* dims, int device, const void* x0, const 
                     const void* l_add, const void* u_add, const double* Q, const double* R, const double* Qf,
                     const void* workspace, void* g, void* l, void* u, void* stream);
 
+/* Reverse mode of the condensing (DESIGN.md section 5 "LTV condensing, adjoint"): the cotangents of (H, A, g, l, u) mapped back
+ * to the inputs of rqp_ltv_condense + rqp_ltv_vectors.  With S = H_sp, Hs = (dH + dH') / 2, e = G x0 + f - yref, T = F Hs:
+ *     Fb = dA + 2 S T + (S e) dg',  eb = S F dg,  sb = eb - dl - du,  dx0 = G'sb,  dyref = -eb,  [Gb | fb] = sb [x0' | 1],
+ *     Sb_kk = F_k T_k' + (F dg)_k e_k'  (diagonal blocks; dR = sum of the u blocks, dQ / dQf of the x blocks, symmetrised),
+ * then, Yb = [Fb | Gb | fb] and X_k = the x_k rows of [F | G | f] (X_0 = [0 | I | 0]), the sweep over the stages
+ *     Lam = Yb[x_N rows];  k = N-1 .. 0:  dAd_k = Lam X_k',  dBd_k = Lam[:, k nu:(k+1) nu] - dAd_k K',  dc_k = Lam[:, f],
+ *                                         Lam <- (A_k - B_k K)' Lam - K' Yb[u_k rows] + Yb[x_k rows]   (k >= 1).
+ * Whatever finite values dA holds at the structural zeros of A = F are not read.  K gets no gradient (a reparametrisation:
+ * u_0 = v_0 - K x0 does not depend on it); the gradients of l_add, u_add are dl, du themselves.
+ * Pointers are DEVICE pointers; the batched ones are in dims.dtype, the weights and their gradients double.               */
+typedef struct rqp_ltv_adjoint_io {
+    const void *Ad, *Bd, *c;     /* the forward inputs of that linearisation (c is not read: f is in the workspace)      */
+    const void *x0, *xref, *uref;/* [batch][nx], and by the flags [batch][horizon][nx], [batch][horizon][nu]             */
+    const double *Q, *R, *Qf, *K;/* as in rqp_ltv_condense (K by RQP_LTV_HAS_K)                                          */
+    const void* workspace;       /* the forward workspace as rqp_ltv_condense left it for these Ad, Bd, c (read only)    */
+    const void *dH, *dA, *dg, *dl, *du; /* cotangents [batch][n][n], [batch][m][n], [batch][n], [batch][m] x 2; NULL = 0 */
+    void *dAd, *dBd, *dc;        /* outputs [batch][horizon][nx][nx], [..][nx][nu], [..][nx]; NULL = not wanted          */
+    void *dx0, *dxref, *duref;   /* outputs shaped like x0, xref, uref; NULL = not wanted                                */
+    double *dQ, *dR, *dQf;       /* outputs [nx][nx], [nu][nu], [nx][nx], summed over the batch, symmetric; NULL = not wanted */
+    void* adjoint_workspace;     /* rqp_ltv_adjoint_workspace_bytes, the caller's; contents need not survive the call    */
+} rqp_ltv_adjoint_io;
+
+/* Bytes of the adjoint's own workspace for these dims (the flags do not change it). */
+int rqp_ltv_adjoint_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes);
+
+/* dims as in the forward calls (flags: HAS_K, HAS_XREF, HAS_UREF say which of K, xref, uref are read; HAS_C and BOUNDS_BATCHED
+ * are accepted and change nothing).  Same contract as the forward: float64 arithmetic, every output rounded once, enqueued on
+ * `stream` of `device` with no allocation and no host synchronisation, a fixed launch chain that depends on dims and on which
+ * pointers are NULL only (capturable in a HIP graph), the caller's current device restored.  Work that only serves outputs that
+ * are not wanted is skipped (dx0 / dxref / duref alone: one kernel; no dAd, dBd, dc: no sweep).  No atomics: the batch sums of
+ * dQ, dR, dQf are added in a fixed order and two calls give the same bits.  RQP_ERR_ARG: io, Ad, Bd, x0, Q, R, Qf, workspace or
+ * adjoint_workspace NULL, or a flag names an input whose pointer is NULL.                                                  */
+int rqp_ltv_condense_adjoint(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io, void* stream);
+
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);
 

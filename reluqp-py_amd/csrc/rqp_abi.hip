@@ -1117,6 +1117,29 @@ int rqp_ltv_vectors(const rqp_ltv_dims* dims, int device, const void* x0, const 
     return RQP_OK;
 }
 
+int rqp_ltv_adjoint_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes) {
+    ltv_err.clear();
+    if (!bytes) return ltv_fail(RQP_ERR_ARG, "rqp_ltv_adjoint_workspace_bytes: bytes is NULL");
+    if (int rc = ltv_check(dims, "rqp_ltv_adjoint_workspace_bytes")) return rc;
+    *bytes = rqp_ltv_adj_ws_bytes(dims);
+    return RQP_OK;
+}
+
+int rqp_ltv_condense_adjoint(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_check(dims, "rqp_ltv_condense_adjoint")) return rc;
+    if (!io || !io->Ad || !io->Bd || !io->x0 || !io->Q || !io->R || !io->Qf || !io->workspace || !io->adjoint_workspace)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_adjoint: io, Ad, Bd, x0, Q, R, Qf, workspace and adjoint_workspace are required");
+    if (((dims->flags & RQP_LTV_HAS_K) && !io->K) || ((dims->flags & RQP_LTV_HAS_XREF) && !io->xref) ||
+        ((dims->flags & RQP_LTV_HAS_UREF) && !io->uref))
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_adjoint: a flag names an input whose pointer is NULL");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_condense_adjoint")) return rc;
+    hipError_t e = rqp_ltv_launch_condense_adjoint(dims, io, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_condense_adjoint: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
 const char* rqp_last_error(const rqp_handle* h) { return h ? h->err.c_str() : ltv_err.c_str(); }
 
 const char* rqp_version(void) { return RQP_VERSION; }

@@ -321,3 +321,6 @@ hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const 
 hipError_t rqp_ltv_launch_vectors(const rqp_ltv_dims* d, const void* x0, const void* xref, const void* uref, const void* l_add,
                                   const void* u_add, const double* Q, const double* R, const double* Qf, const void* ws, void* g,
                                   void* l, void* u, hipStream_t s);
+// reverse mode of the condensing (rqp_condense_adj.hip)
+size_t rqp_ltv_adj_ws_bytes(const rqp_ltv_dims* d);
+hipError_t rqp_ltv_launch_condense_adjoint(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io, hipStream_t s);

@@ -25,7 +25,8 @@ ABI_SYMBOLS = (
     "rqp_update_settings",
     "rqp_warm_start", "rqp_clear_primal_dual", "rqp_solve", "rqp_iterate", "rqp_compute_residuals",
     "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity",
-    "rqp_ltv_workspace_bytes", "rqp_ltv_condense", "rqp_ltv_vectors", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
+    "rqp_ltv_workspace_bytes", "rqp_ltv_condense", "rqp_ltv_vectors", "rqp_ltv_adjoint_workspace_bytes",
+    "rqp_ltv_condense_adjoint", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
     "rqp_last_error", "rqp_version",
 )
 
@@ -78,6 +79,13 @@ LTV_HAS_K, LTV_HAS_C, LTV_HAS_XREF, LTV_HAS_UREF, LTV_BOUNDS_BATCHED = 1, 2, 4, 
 class LtvDims(ctypes.Structure):
     """struct rqp_ltv_dims."""
     _fields_ = [(f, ctypes.c_int32) for f in ("batch", "nx", "nu", "horizon", "dtype", "flags")]
+
+
+class LtvAdjointIO(ctypes.Structure):
+    """struct rqp_ltv_adjoint_io: device pointers (None = NULL)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf", "K", "workspace",
+                                                "dH", "dA", "dg", "dl", "du", "dAd", "dBd", "dc", "dx0", "dxref", "duref",
+                                                "dQ", "dR", "dQf", "adjoint_workspace")]
 
 
 class CInfo(ctypes.Structure):
@@ -138,6 +146,8 @@ def load():
         "rqp_ltv_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.POINTER(ctypes.c_size_t)]),
         "rqp_ltv_condense": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 11),
         "rqp_ltv_vectors": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 13),
+        "rqp_ltv_adjoint_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.POINTER(ctypes.c_size_t)]),
+        "rqp_ltv_condense_adjoint": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, ctypes.POINTER(LtvAdjointIO), vp]),
         "rqp_kernel_name": (ctypes.c_char_p, [H]),
         "rqp_destroy": (ctypes.c_int, [H]),
         "rqp_strerror": (ctypes.c_char_p, [ctypes.c_int]),

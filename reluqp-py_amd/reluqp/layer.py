@@ -13,7 +13,7 @@ Host code is plumbing: handle bookkeeping, reshapes and casts.  The batch sums o
 """
 import torch
 
-from reluqp import _cabi
+from reluqp import _cabi, mpc
 from reluqp.reluqpth import ReLU_QP
 
 _NAMES = ("dH", "dg", "dA", "dl", "du")
@@ -133,3 +133,112 @@ class ReLUQPLayer(torch.nn.Module):
             solver.update(g=g, l=l, u=u)
         solver.solve()
         return solver, shapes
+
+
+class LTVCondenseFunction(torch.autograd.Function):
+    """``LTVCondenseFunction.apply(condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add)`` -> ``(H, A, g, l, u)``: the
+    condensed QPs of a batch of LTV plants (C-ABI rqp_ltv_condense + rqp_ltv_vectors) with their reverse mode (C-ABI
+    rqp_ltv_condense_adjoint, DESIGN.md section 5 "LTV condensing, adjoint").  ``condenser`` is an ``mpc.LTVCondenser``; Ad
+    [B, N, nx, nx], Bd [B, N, nx, nu], x0 [B, nx] are device tensors of one precision, c [B, N, nx], xref [B, N, nx], uref
+    [B, N, nu] may be None, Q, R, Qf are symmetric tensors (their symmetric part is used, their gradients are symmetric),
+    l_add / u_add [m] or [B, m].  Only the gradients that ``needs_input_grad`` names are computed."""
+
+    @staticmethod
+    def forward(ctx, condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add):
+        cd = condenser
+        dtype, device, B = Ad.dtype, Ad.device, Ad.shape[0]
+        slot = cd.slot(B, device, dtype)
+        f64 = lambda W: (0.5 * (W.detach() + W.detach().transpose(0, 1))).to(device=device, dtype=torch.float64).contiguous()
+        Qd, Rd, Qfd = f64(Q), f64(R), f64(Qf)
+        w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+        det = lambda t: None if t is None else t.detach().contiguous()
+        Ad, Bd, c, x0, xref, uref = (det(t) for t in (Ad, Bd, c, x0, xref, uref))
+        slot["stamp"] = ctx.stamp = cd.next_stamp()
+        H, A = mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c)
+        g, l, u = mpc.ltv_vectors_device((cd.nx, cd.nu, cd.horizon, cd.K is not None, c is not None), x0, l_add.detach(),
+                                         u_add.detach(), w, slot["ws"], xref=xref, uref=uref)
+        ctx.condenser, ctx.slot = cd, slot
+        ctx.meta = (Q.dtype, R.dtype, Qf.dtype, l_add.dim(), u_add.dim(), l_add.dtype, u_add.dtype)
+        ctx.save_for_backward(Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd)
+        ctx.set_materialize_grads(False)
+        return H, A, g, l, u
+
+    @staticmethod
+    def backward(ctx, gH, gA, gg, gl, gu):
+        Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors
+        slot = ctx.slot
+        names = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
+        need = ctx.needs_input_grad
+        want = tuple(k for k, nd in zip(names, need[1:10]) if nd)
+        grads = [None] * 12
+        if want:
+            w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+            if slot["stamp"] != ctx.stamp:               # a later forward has overwritten the workspace: condense these stages again
+                Hs, As = ctx.condenser.recondense_outputs(slot, Ad.shape[0], Ad.device, Ad.dtype)
+                mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, H=Hs, A=As)
+                slot["stamp"] = ctx.stamp
+            out = mpc.condense_ltv_adjoint_device(Ad, Bd, x0, w, slot["ws"], slot["adj"], xref=xref, uref=uref, dH=gH, dA=gA,
+                                                  dg=gg, dl=gl, du=gu, want=want)
+            qdt = dict(Q=ctx.meta[0], R=ctx.meta[1], Qf=ctx.meta[2])
+            for i, k in enumerate(names):
+                if k in out:
+                    grads[1 + i] = out[k].to(qdt[k]) if k in qdt else out[k]
+        for i, gb, dim, dt in ((10, gl, ctx.meta[3], ctx.meta[5]), (11, gu, ctx.meta[4], ctx.meta[6])):
+            if need[i] and gb is not None:
+                grads[i] = (gb if dim == 2 else gb.sum(0)).to(dt)
+        return tuple(grads)
+
+
+class LTVMPCLayer(torch.nn.Module):
+    """Differentiable MPC on a batch of LTV plants: ``u0, v = LTVMPCLayer(nx, nu, horizon, u_max, x_max, K=None)(Ad, Bd, x0, Q, R,
+    Qf, c=None, xref=None, uref=None)``.  The stages are condensed on the device (``LTVCondenseFunction``), the QPs solved by a
+    ``ReLUQPLayer`` on per-instance matrices (``setup_kwargs`` are its keyword arguments; its defaults ``differentiable=True,
+    polish=True``), and the first input is u0 = v[:, :nu] - x0 K' [B, nu]; v [B, n] is the whole QP solution.  Gradients flow to
+    Ad, Bd, c, x0, xref, uref and to the weights Q, R, Qf (shared by the batch: summed over it).  The box |u| <= u_max,
+    |x| <= x_max and the gain K are constants of the layer."""
+
+    def __init__(self, nx, nu, horizon, u_max, x_max, K=None, **setup_kwargs):
+        super().__init__()
+        self.condenser = mpc.LTVCondenser(nx, nu, horizon, K=K)
+        self.nx, self.nu, self.horizon = self.condenser.nx, self.condenser.nu, self.condenser.horizon
+        _, self.l_add, self.u_add = mpc.box_constraints(self.nx, self.nu, self.horizon, u_max, x_max)
+        self.qp = ReLUQPLayer(**setup_kwargs)
+        self._const = {}
+
+    def _check(self, Ad, Bd, x0, Q, R, Qf, c, xref, uref):
+        nx, nu, N = self.nx, self.nu, self.horizon
+        for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("Q", Q), ("R", R), ("Qf", Qf)):
+            if not torch.is_tensor(t):
+                raise ValueError("%s must be a torch tensor" % name)
+        B, Ns, nxs, nus = mpc._ltv_shapes(Ad, Bd)
+        if (Ns, nxs, nus) != (N, nx, nu):
+            raise ValueError("stages of shape (N=%d, nx=%d, nu=%d), expected (%d, %d, %d)" % (Ns, nxs, nus, N, nx, nu))
+        for name, t, shape in (("x0", x0, (B, nx)), ("c", c, (B, N, nx)), ("xref", xref, (B, N, nx)), ("uref", uref, (B, N, nu))):
+            if t is not None and tuple(t.shape) != shape:
+                raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), shape))
+        if tuple(Q.shape) != (nx, nx) or tuple(Qf.shape) != (nx, nx) or tuple(R.shape) != (nu, nu):
+            raise ValueError("Q, Qf must be [%d, %d] and R [%d, %d]" % (nx, nx, nu, nu))
+        # symmetric up to rounding, as BatchedLTVMPC asks (the symmetric part is what is used); the three tests share one read-back
+        asym = torch.stack([(W.detach() - W.detach().transpose(0, 1)).abs().max() - 1e-9 * W.detach().abs().max()
+                            for W in (Q, R, Qf)]).tolist()
+        for name, a in zip(("Q", "R", "Qf"), asym):
+            if a > 0:
+                raise ValueError("%s must be symmetric" % name)
+        if Ad.dtype not in (torch.float32, torch.float64) or any(t is not None and t.dtype != Ad.dtype for t in (Bd, x0, c, xref, uref)):
+            raise ValueError("Ad, Bd, x0 (c, xref, uref) must share one precision, float32 or float64")
+        if Ad.device.type != "cuda":
+            raise _cabi.RqpUnavailable("LTVMPCLayer needs a HIP device; the MI355X build has no CPU path")
+        return B
+
+    def forward(self, Ad, Bd, x0, Q, R, Qf, c=None, xref=None, uref=None):
+        self._check(Ad, Bd, x0, Q, R, Qf, c, xref, uref)
+        key = (str(Ad.device), Ad.dtype)
+        if key not in self._const:
+            t = lambda a: None if a is None else torch.as_tensor(a, dtype=Ad.dtype, device=Ad.device)
+            self._const[key] = (t(self.l_add), t(self.u_add), t(self.condenser.K))
+        l_add, u_add, K = self._const[key]
+        H, A, g, l, u = LTVCondenseFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add)
+        out = self.qp(H, g, A, l, u)
+        v = out[0]
+        u0 = v[:, :self.nu] if K is None else v[:, :self.nu] - x0 @ K.transpose(0, 1)
+        return u0, v

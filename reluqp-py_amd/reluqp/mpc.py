@@ -444,6 +444,88 @@ def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None):
     return g, np.asarray(l_add, dtype=F.dtype) - s, np.asarray(u_add, dtype=F.dtype) - s
 
 
+_LTV_VJP_KEYS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf", "l_add", "u_add", "K")
+
+
+def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=None, uref=None,
+                     dH=None, dA=None, dg=None, dl=None, du=None):
+    """Reverse of ``condense_ltv`` + ``ltv_vectors`` on the host (numpy): the cotangents dH [n, n], dA [m, n], dg [n],
+    dl, du [m] of (H, A, g, l, u) (an absent one is zero) mapped back to the inputs.  One instance, or a leading batch axis
+    on Ad, Bd (and on c, x0, xref, uref, the cotangents, and l_add / u_add when they are [B, m]).  Returns a dict with the
+    gradients of Ad, Bd, c, x0, xref, uref, l_add, u_add (batched like the inputs; l_add / u_add summed over the batch when
+    shared) and of Q, R, Qf, K (summed over the batch; Q, R, Qf symmetric).  K is a reparametrisation -- u_0 = v_0 - K x0 does
+    not depend on it in exact arithmetic -- so its entry only states the derivative of the condensing outputs.
+
+    With S = H_sp, Hs = sym(dH), e = G x0 + f - yref, T = F Hs:
+        Fb = dA + 2 S T + (S e) dg',  eb = S F dg,  sb = eb - dl - du,  x0b = G'sb,  yrefb = -eb,  [Gb | fb] = sb [x0' | 1],
+        Sb = F T' + (F dg) e' (its diagonal blocks give Rb, Qb, Qfb),
+    and the reverse sweep over the stages, Lam = the x_N rows of Yb = [Fb | Gb | fb], X_k = the x_k rows of [F | G | f]:
+        k = N-1 .. 0:  Aclb = Lam X_k',  Adb_k = Aclb,  Bdb_k = Lam[:, k nu:(k+1) nu] - Aclb K',  cb_k = Lam[:, f],
+                       Lam <- Acl_k' Lam - K' Yb[u_k rows] + Yb[x_k rows]   (k >= 1)."""
+    Ad, Bd = np.asarray(Ad), np.asarray(Bd)
+    if Ad.ndim == 4:
+        B = Ad.shape[0]
+        at = lambda a, b: None if a is None else np.asarray(a)[b]
+        lu = lambda a, b: np.asarray(a)[b] if np.ndim(a) == 2 else a
+        outs = [condense_ltv_vjp(Ad[b], Bd[b], Q, R, Qf, np.asarray(x0)[b], lu(l_add, b), lu(u_add, b), K=K, c=at(c, b),
+                                 xref=at(xref, b), uref=at(uref, b), dH=at(dH, b), dA=at(dA, b), dg=at(dg, b), dl=at(dl, b),
+                                 du=at(du, b)) for b in range(B)]
+        res = {}
+        for k in _LTV_VJP_KEYS:
+            shared = k in ("Q", "R", "Qf", "K") or (k == "l_add" and np.ndim(l_add) == 1) or (k == "u_add" and np.ndim(u_add) == 1)
+            st = np.stack([o[k] for o in outs])
+            res[k] = st.sum(0) if shared else st
+        return res
+    dt = np.result_type(Ad.dtype, np.float64)                  # float64, or wider when the caller passes longdouble
+    N, nx, nu = Ad.shape[0], Ad.shape[1], Bd.shape[2]
+    blk, n, m = nx + nu, N * nu, N * (nx + nu)
+    cast = lambda a, shape: np.zeros(shape, dtype=dt) if a is None else np.asarray(a).astype(dt).reshape(shape)
+    Ad, Bd = Ad.astype(dt), Bd.astype(dt)
+    Kz, x0 = cast(K, (nu, nx)), cast(x0, (nx,))
+    xref, uref = cast(xref, (N, nx)), cast(uref, (N, nu))
+    Hb, Ab, gb, lb, ub = cast(dH, (n, n)), cast(dA, (m, n)), cast(dg, (n,)), cast(dl, (m,)), cast(du, (m,))
+    cond = condense_ltv(Ad, Bd, np.asarray(Q).astype(dt), np.asarray(R).astype(dt), np.asarray(Qf).astype(dt), K=Kz,
+                        c=None if c is None else np.asarray(c).astype(dt))
+    F, G, f, S = cond["F"], cond["G"], cond["f"], cond["H_sp"]
+    e = G @ x0 + f - np.hstack([uref, xref]).reshape(-1)
+    Hs = (Hb + Hb.T) / 2
+    T = F @ Hs
+    Fb = Ab + 2 * (S @ T) + np.outer(S @ e, gb)
+    eb = S @ (F @ gb)
+    sb = eb - lb - ub
+    Yb = np.hstack([Fb, np.outer(sb, x0), sb[:, None]])
+    Fg = F @ gb
+    Rb, Qb, Qfb = np.zeros((nu, nu), dtype=dt), np.zeros((nx, nx), dtype=dt), np.zeros((nx, nx), dtype=dt)
+    for k in range(N):                                         # only the diagonal blocks of Sb = F T' + (F dg) e' are needed
+        rk = slice(k * blk, (k + 1) * blk)
+        Sk = F[rk] @ T[rk].T + np.outer(Fg[rk], e[rk])
+        Rb += Sk[:nu, :nu]
+        xb = Sk[nu:, nu:]
+        if k == N - 1:
+            Qfb += xb
+        else:
+            Qb += xb
+    Rb, Qb, Qfb = ((W + W.T) / 2 for W in (Rb, Qb, Qfb))
+    Y = np.hstack([F, G, f[:, None]])
+    X0 = np.zeros((nx, n + nx + 1), dtype=dt)
+    X0[:, n:n + nx] = np.eye(nx, dtype=dt)
+    X = [X0] + [Y[k * blk + nu:(k + 1) * blk] for k in range(N)]
+    Adb, Bdb, cb, Kb = np.zeros_like(Ad), np.zeros_like(Bd), np.zeros((N, nx), dtype=dt), np.zeros((nu, nx), dtype=dt)
+    Lam = Yb[(N - 1) * blk + nu:N * blk].copy()
+    for k in range(N - 1, -1, -1):
+        Yu = Yb[k * blk:k * blk + nu]
+        Aclb = Lam @ X[k].T
+        Adb[k] = Aclb
+        Bdb[k] = Lam[:, k * nu:(k + 1) * nu] - Aclb @ Kz.T
+        cb[k] = Lam[:, -1]
+        Kb -= Yu @ X[k].T + Bd[k].T @ Aclb
+        if k >= 1:
+            Lam = (Ad[k] - Bd[k] @ Kz).T @ Lam - Kz.T @ Yu + Yb[(k - 1) * blk + nu:k * blk]
+    yr = (-eb).reshape(N, blk)
+    return dict(Ad=Adb, Bd=Bdb, c=cb, x0=G.T @ sb, xref=yr[:, nu:].copy(), uref=yr[:, :nu].copy(), Q=Qb, R=Rb, Qf=Qfb,
+                l_add=lb, u_add=ub, K=Kb)
+
+
 class _LtvWeights(object):
     """Q, R, Qf (and K) as float64 device tensors (what the C-ABI reads), cached per device."""
 
@@ -458,6 +540,134 @@ class _LtvWeights(object):
             t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64, device=device)
             self._dev[key] = tuple(t(a) for a in (self.Q, self.R, self.Qf, self.K))
         return self._dev[key]
+
+
+class _LtvTensorWeights(_LtvWeights):
+    """Q, R, Qf (K) that already are float64 device tensors (the autograd path: the weights are torch inputs)."""
+
+    def __init__(self, Q, R, Qf, K):
+        self._t = (Q, R, Qf, K)
+
+    def on(self, device):
+        return self._t
+
+
+def ltv_adjoint_workspace(batch, nx, nu, horizon, device):
+    """The float64 workspace of ``condense_ltv_adjoint_device`` for these sizes (a device tensor)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    _ltv_check_sizes(nx, nu, horizon)
+    lib = _cabi.load()
+    dims = _cabi.LtvDims(batch=batch, nx=nx, nu=nu, horizon=horizon, dtype=_cabi.RQP_F64, flags=0)
+    nbytes = ctypes.c_size_t()
+    _cabi.check(None, lib.rqp_ltv_adjoint_workspace_bytes(ctypes.byref(dims), ctypes.byref(nbytes)),
+                "rqp_ltv_adjoint_workspace_bytes", handleless=True)
+    return torch.empty(nbytes.value // 8, dtype=torch.float64, device=device)
+
+
+LTV_ADJOINT_OUTPUTS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
+
+
+def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspace, xref=None, uref=None, dH=None, dA=None,
+                                dg=None, dl=None, du=None, want=LTV_ADJOINT_OUTPUTS):
+    """Reverse of ``condense_ltv_device`` + ``ltv_vectors_device`` on the device (C-ABI rqp_ltv_condense_adjoint; the host
+    statement is ``condense_ltv_vjp``).  ``workspace`` is the forward workspace as ``condense_ltv_device`` left it for these
+    Ad, Bd (c); dH [B, n, n], dA [B, m, n], dg [B, n], dl, du [B, m] are the cotangents (None = zero), device tensors of
+    Ad's precision.  ``want`` names the gradients to compute: a dict of those comes back (Ad, Bd, c, x0, xref, uref in Ad's
+    precision; Q, R, Qf float64, summed over the batch).  Enqueued on the current stream."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    B, N, nx, nu = _ltv_shapes(Ad, Bd)
+    _ltv_check_sizes(nx, nu, N)
+    if not torch.is_tensor(Ad) or Ad.device.type != "cuda":
+        raise _cabi.RqpUnavailable("condense_ltv_adjoint_device needs device tensors; the host restatement is condense_ltv_vjp")
+    unknown = [k for k in want if k not in LTV_ADJOINT_OUTPUTS]
+    if unknown:
+        raise ValueError("unknown gradient name(s) %s; known: %s" % (unknown, LTV_ADJOINT_OUTPUTS))
+    dtype, device = Ad.dtype, Ad.device
+    n, m = N * nu, N * (nx + nu)
+    w = weights if isinstance(weights, _LtvWeights) else _LtvWeights(nx, nu, *weights)
+    Q, R, Qf, K = w.on(device)
+    opt = lambda t, shape, name: None if t is None else _ltv_in(t, shape, dtype, device, name)
+    Ad, Bd, x0 = opt(Ad, (B, N, nx, nx), "Ad"), opt(Bd, (B, N, nx, nu), "Bd"), opt(x0, (B, nx), "x0")
+    xref, uref = opt(xref, (B, N, nx), "xref"), opt(uref, (B, N, nu), "uref")
+    dH, dA, dg = opt(dH, (B, n, n), "dH"), opt(dA, (B, m, n), "dA"), opt(dg, (B, n), "dg")
+    dl, du = opt(dl, (B, m), "dl"), opt(du, (B, m), "du")
+    shapes = dict(Ad=(B, N, nx, nx), Bd=(B, N, nx, nu), c=(B, N, nx), x0=(B, nx), xref=(B, N, nx), uref=(B, N, nu),
+                  Q=(nx, nx), R=(nu, nu), Qf=(nx, nx))
+    out = {k: torch.empty(shapes[k], dtype=torch.float64 if k in ("Q", "R", "Qf") else dtype, device=device) for k in want}
+    io = _cabi.LtvAdjointIO()
+    for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("xref", xref), ("uref", uref), ("Q", Q), ("R", R), ("Qf", Qf), ("K", K),
+                    ("workspace", workspace), ("dH", dH), ("dA", dA), ("dg", dg), ("dl", dl), ("du", du),
+                    ("adjoint_workspace", adjoint_workspace)):
+        setattr(io, name, None if t is None else t.data_ptr())
+    for k, t in out.items():
+        setattr(io, "d" + k, t.data_ptr())
+    flags = ((_cabi.LTV_HAS_K if K is not None else 0) | (_cabi.LTV_HAS_XREF if xref is not None else 0)
+             | (_cabi.LTV_HAS_UREF if uref is not None else 0))
+    dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
+                         flags=flags)
+    lib = _cabi.load()
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_condense_adjoint(ctypes.byref(dims), device.index or 0, ctypes.byref(io), stream),
+                    "rqp_ltv_condense_adjoint", handleless=True)
+    return out
+
+
+class LTVCondenser(object):
+    """What ``reluqp.layer.LTVCondenseFunction`` keeps between calls: the sizes, the shared gain K, and per (batch, device)
+    one forward workspace, one adjoint workspace and scratch H / A.  The forward workspace (F, H_sp F, [G | f]: the largest
+    tensors of the condensing) is never cloned: ``stamp`` says which forward's linearisation it holds, and a backward whose
+    forward has been overwritten by a later one condenses its saved (small) inputs again before it differentiates.
+    Memory: a slot lives as long as the condenser and holds 8 (2 m n + (m + n)(nx + 1)) bytes per instance forward and
+    8 (m n + 4 m + N (nu^2 + nx^2)) bytes per instance adjoint workspace (0.45 MB + 0.22 MB at (12, 4, 20)), for every distinct
+    (batch, device, dtype) the layer has seen; ``release()`` drops them.  The H / A outputs that a re-condense discards are
+    allocated by the first backward that needs one."""
+
+    def __init__(self, nx, nu, horizon, K=None):
+        nx, nu, horizon = int(nx), int(nu), int(horizon)
+        _ltv_check_sizes(nx, nu, horizon)
+        self.nx, self.nu, self.horizon = nx, nu, horizon
+        self.n, self.m = horizon * nu, horizon * (nx + nu)
+        if K is not None:
+            if getattr(K, "requires_grad", False):
+                raise ValueError("K cannot require a gradient: the pre-stabilising gain is a reparametrisation of the inputs "
+                                 "(u_0 = v_0 - K x0 does not depend on it), pass K.detach()")
+            K = np.asarray(K.detach().cpu() if hasattr(K, "detach") else K, dtype=np.float64)
+            if K.shape != (nu, nx):
+                raise ValueError("K has shape %s, expected (%d, %d)" % (K.shape, nu, nx))
+        self.K = K
+        self._slots = {}
+        self._count = 0
+
+    def slot(self, B, device, dtype):
+        import torch
+        key = (B, str(device), dtype)
+        if key not in self._slots:
+            self._slots[key] = dict(ws=ltv_workspace(B, self.nx, self.nu, self.horizon, device),
+                                    adj=ltv_adjoint_workspace(B, self.nx, self.nu, self.horizon, device),
+                                    H=None, A=None,
+                                    K=None if self.K is None else torch.as_tensor(self.K, dtype=torch.float64, device=device),
+                                    stamp=0)
+        return self._slots[key]
+
+    def recondense_outputs(self, slot, B, device, dtype):
+        import torch
+        if slot["H"] is None:
+            slot["H"] = torch.empty((B, self.n, self.n), dtype=dtype, device=device)
+            slot["A"] = torch.empty((B, self.m, self.n), dtype=dtype, device=device)
+        return slot["H"], slot["A"]
+
+    def release(self):
+        """Drop every workspace (the next forward allocates again; a pending backward of an earlier forward must not follow)."""
+        self._slots = {}
+
+    def next_stamp(self):
+        self._count += 1
+        return self._count
 
 
 def ltv_workspace(batch, nx, nu, horizon, device):

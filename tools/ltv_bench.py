@@ -3,7 +3,9 @@ include/rqp_abi.h rqp_ltv_condense / rqp_ltv_vectors) next to the solver calls i
 
 At B = 4096, (nx, nu, N) = (12, 4, 20) -> (n, m) = (80, 320), float32 and float64 outputs: device time (HIP events, median of
 --reps calls after warm-up) of `condense` (transition + Hessian kernels) and `vectors`, and of update(Hx, Ax) and a
-warm-started solve() of the handle set up on that data, in the same run.  The host path it replaces -- numpy condense_ltv
+warm-started solve() of the handle set up on that data, in the same run; then the backward column: the condensing's reverse
+mode (condense_ltv_adjoint_device, rqp_ltv_condense_adjoint: every cotangent given, every gradient wanted) next to the forward
+`condense` and to adjoint() of a differentiable handle set up on the same data.  The host path it replaces -- numpy condense_ltv
 over the batch on --workers processes plus the host-to-device copy of (H, A) -- is timed on --host-batch instances and
 scaled to B.  Per-kernel times: run the same command under `rocprofv3 --kernel-trace --stats`.
 
@@ -75,6 +77,7 @@ def main():
     host_s, host_out = _host_baseline(Ad[:hb], Bd[:hb], Q, R, P, K, args.workers)
 
     import torch
+    import reluqp.reluqpth as reluqpth
     dev = torch.device("cuda:0")
     res = []
     for prec in (torch.float32, torch.float64):
@@ -100,6 +103,24 @@ def main():
             s.update(g=buf["g"], l=buf["l"], u=buf["u"])
             s.solve()
         out["warm_solve_ms"], _, _ = _timed(torch, warm_solve, args.reps)
+        # backward: the condensing's adjoint (the workspace holds this linearisation) and the QP adjoint of the same handle
+        adj_ws = mpc.ltv_adjoint_workspace(B, NX, NU, N, dev)
+        cot = dict(dH=t(rs.randn(B, ctl.n, ctl.n)), dA=t(rs.randn(B, ctl.m, ctl.n)), dg=t(rs.randn(B, ctl.n)),
+                   dl=t(rs.randn(B, ctl.m)), du=t(rs.randn(B, ctl.m)))
+        back = lambda: mpc.condense_ltv_adjoint_device(Adt, Bdt, xt, ctl.weights, buf["ws"], adj_ws, xref=xr, **cot)
+        out["condense_adjoint_ms"], out["condense_adjoint_min_ms"], out["condense_adjoint_max_ms"] = _timed(torch, back, args.reps)
+        only_x0 = lambda: mpc.condense_ltv_adjoint_device(Adt, Bdt, xt, ctl.weights, buf["ws"], adj_ws, xref=xr, want=("x0",), **cot)
+        out["condense_adjoint_x0_only_ms"], _, _ = _timed(torch, only_x0, args.reps)
+        # (a second handle on the same data: the columns above stay those of a handle without the adjoint's workspace)
+        sd = reluqpth.ReLU_QP()
+        sd.setup(buf["H"], buf["g"], buf["A"], buf["l"], buf["u"], device=dev, precision=prec, eps_abs=1e-3, differentiable=True)
+        sd.solve()
+        sd.synchronous = False
+        dx = t(rs.randn(B, ctl.n))
+        out["qp_adjoint_ms"], _, _ = _timed(torch, lambda: sd.adjoint(dx), args.reps)
+        del sd
+        out["condense_adjoint_over_condense"] = out["condense_adjoint_ms"] / out["condense_ms"]
+        del adj_ws, cot
         torch.cuda.synchronize()
         out["condense_over_update_mats"] = out["condense_ms"] / out["update_mats_ms"]
         # the host path: numpy over the batch (scaled from --host-batch instances) + the copy of its (H, A) to the device
