@@ -51,6 +51,14 @@ __device__ __forceinline__ float swsum16(float a, float b) {      // even rows: 
     asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     return a + b;
 }
+__device__ __forceinline__ float swmax32(float a, float b) {      // lower half: max(a.lo, a.hi) ; upper half: max(b.lo, b.hi)
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    return fmaxf(a, b);
+}
+__device__ __forceinline__ float swmax16(float a, float b) {      // even rows: max(a.even, a.odd) ; odd rows: max(b.even, b.odd)
+    asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    return fmaxf(a, b);
+}
 __device__ __forceinline__ float wave_max(float v) {              // max over the 64 lanes, every lane gets it (NaN-free inputs)
     v = fmaxf(v, dpp2<0xB1>(v));
     v = fmaxf(v, dpp2<0x4E>(v));
@@ -105,9 +113,9 @@ struct Res2Cfg {
     static_assert(8 * KR >= CW && 8 * KC >= N && M <= 2 * NT && KC == CQ && NQ == 2, "tile shape");
     static constexpr size_t lds_bytes() {
         return (size_t)M * 8 * 4 + ND * 8 + 16 * 8       // zt64 lam64 z64 inv64 | x64 | redd
-               + (size_t)M * 4 * 4                       // lT uT rv32 nu
+               + (size_t)M * 4 * 5                       // lT uT rv32 nu cT
                + (size_t)ND * 4 * 6                      // xin xnat dxv hx gT dvec
-               + (size_t)NW * M * 4 + 64 * 4             // part, red
+               + (size_t)NW * M * 4 + 96 * 4             // part, red (two check buffers + the rho ladder)
                + (size_t)HU * NT * 16;                   // Hs
     }
 };
@@ -117,6 +125,9 @@ struct Res2Cfg {
 // KH = true: the K(rho) tile is stored as fp16 row pairs (rqp_dims.tile_dtype = RQP_TILE_F16, BASELINE config 5): half the
 // registers and half the reload bytes; products accumulate in float32 (v_fma_mix_f32 reads the half operand directly), the
 // per-(matrix, rho) power-of-two scale Kscale keeps the entries inside the fp16 range.  K only preconditions dx = -K d.
+// dbg slots per (instance, wave): 0..7 the segments of an ordinary iteration; 8..21 the parts of a check (names in solve_t);
+// 22 checks, 23 rho moves, 24 iterations
+constexpr int NSEG = 25;
 template <class C, bool DIAG, bool KH, bool KD = false>
 __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs a, const float* __restrict__ Apack,
                                                       const float* __restrict__ Kpack,
@@ -135,16 +146,17 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
     float* uT = lT + M;
     float* rv32 = uT + M;
     float* nu = rv32 + M;                                 // [M] nu (lam at a check)
-    float* xin = nu + M;                                  // [ND] float(x), slot order (SW per wave)
+    float* cT = nu + M;                                   // [M] c_i (1 in the padding rows): rho_i = rho c_i at a rho move
+    float* xin = cT + M;                                  // [ND] float(x), slot order (SW per wave)
     float* xnat = xin + ND;                               // [ND] float(x), natural order (rows of H)
     float* dxv = xnat + ND;                               // [ND] dx
     float* hx = dxv + ND;                                 // [ND] H x
     float* gT = hx + ND;                                  // [ND]
     float* dvec = gT + ND;                                // [ND] d (A' lam at a check)
     float* part = dvec + ND;                              // [NW][M] per-wave partial row sums of A dx
-    float* red = part + NW * M;                           // [64]
-    float* Hs = red + 64;                                 // [HU][NT][4]
-    static_assert(((size_t)M * 8 * 4 + ND * 8 + 16 * 8 + (size_t)M * 4 * 4 + ND * 4 * 6 + NW * M * 4 + 64 * 4) % 16 == 0,
+    float* red = part + NW * M;                           // [96]: two [NW][8] check buffers (by check parity), the rho ladder
+    float* Hs = red + 96;                                 // [HU][NT][4]
+    static_assert(((size_t)M * 8 * 4 + ND * 8 + 16 * 8 + (size_t)M * 4 * 5 + ND * 4 * 6 + NW * M * 4 + 96 * 4) % 16 == 0,
                   "H image must start 16-byte aligned");
 
     const int n = a.n, m = a.m;
@@ -207,7 +219,7 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         for (int u = 0; u < HU; ++u) ((float4*)Hs)[u * NT + tid] = Hp[u * NT + tid];
     }
     int ri = a.rho_ind[b];
-    float* rhoL = red + 32;                               // [32] the rho ladder: read at every check (LDS, not a dependent global load)
+    float* rhoL = red + 64;                               // [32] the rho ladder: read at every check (LDS, not a dependent global load)
     if (tid < 32) rhoL[tid] = (tid < a.nrho) ? (float)a.rhos[tid] : 0.f;     // (nrho <= 32: res2_pick)
     typedef typename std::conditional<KH, h2, f2>::type kpair_t;      // a row pair of K: two floats, or two halves in one dword
     kpair_t kr[KP][KC];
@@ -220,7 +232,9 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         int j = jl - wb;                                            // K slot (modes 1 / 2 of a windowed handle: rqp_iterate /
         j = j < 0 ? 0 : (j >= a.kwin ? a.kwin - 1 : j);             // rqp_compute_residuals re-centre the windows first)
         if constexpr (!KD) {
-            const kpair_t* Kp = (const kpair_t*)Kpack + (mat * a.kwin + j) * (size_t)KE2 * NT + tid;
+            int tid_k = tid;                                        // (opaque copy: the per-lane base address of this rare path is
+            asm volatile("" : "+v"(tid_k));                         //  otherwise hoisted out of the solve loop and spilled)
+            const kpair_t* Kp = (const kpair_t*)Kpack + (mat * a.kwin + j) * (size_t)KE2 * NT + tid_k;
 #pragma unroll
             for (int kp = 0; kp < KP; ++kp)
 #pragma unroll
@@ -278,6 +292,7 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         lT[i] = in ? ((const float*)a.l)[(size_t)b * m + i] : 0.f;
         uT[i] = in ? ((const float*)a.u)[(size_t)b * m + i] : 0.f;
         nu[i] = 0.f;
+        cT[i] = in ? cg[i] : 1.f;
     }
     set_rho_rows(ri);
     for (int i = tid; i < ND; i += NT) {                  // slot i <-> column SW-block (i / SW), offset (i % SW)
@@ -428,7 +443,72 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         }
     };
     constexpr std::true_type YES{};
-    constexpr std::false_type NO{};
+    // The two transposed products of a check in ONE pass: outA = A' w, outH = H x, with separate accumulators for the A part and
+    // the H part of every column (each sum in exactly the order of prod_At's A-only / H-only column sums).  Alone, the H part
+    // was two dependent packed FMAs per column -- pure latency; here the four chains of a column pair interleave.
+    auto prod_At_chk = [&](const float* w, float* outA, float* outH) {
+        f2 wr[RP];
+        f2 wx[HP];
+#pragma unroll
+        for (int rp = 0; rp < RP; ++rp) wr[rp] = ((const f2*)(w + RB * pl))[rp];
+        {
+            const float4 xv = *(const float4*)(xnat + HR * pl);
+            wx[0] = (f2){xv.x, xv.y};
+            wx[1] = (f2){xv.z, xv.w};
+        }
+        auto hload = [&](int c) -> float4 { return ((const float4*)Hs)[c * NT + tid]; };
+        float sA[H1], sH[H1];
+        float4 hcur = hload(0), hnext = {0.f, 0.f, 0.f, 0.f};
+        if (H1 < CQ) hnext = hload(H1);
+#pragma unroll
+        for (int i = 0; i < H1; ++i) {
+            const bool pair = (i + H1 < CQ);
+            float4 hc2 = hcur, hn2 = hnext;                              // next pair's H rows: requested before this pair's FMAs
+            if (i + 1 < H1) hc2 = hload(i + 1);
+            if (i + 1 + H1 < CQ) hn2 = hload(i + 1 + H1);
+            f2 a0 = {0.f, 0.f}, a1 = {0.f, 0.f};
+            f2 h0 = __builtin_elementwise_fma((f2){hcur.x, hcur.y}, wx[0], (f2){0.f, 0.f}), h1 = {0.f, 0.f};
+            if (pair) h1 = __builtin_elementwise_fma((f2){hnext.x, hnext.y}, wx[0], h1);
+#pragma unroll
+            for (int rp = 0; rp < RP; ++rp) {
+                a0 = __builtin_elementwise_fma(ar[rp][i], wr[rp], a0);
+                if (pair) a1 = __builtin_elementwise_fma(ar[rp][i + H1], wr[rp], a1);
+            }
+            h0 = __builtin_elementwise_fma((f2){hcur.z, hcur.w}, wx[1], h0);
+            if (pair) h1 = __builtin_elementwise_fma((f2){hnext.z, hnext.w}, wx[1], h1);
+            const float ca0 = a0.x + a0.y, ch0 = h0.x + h0.y;
+            sA[i] = pair ? swsum32(ca0, a1.x + a1.y) : swsum32(ca0, ca0);
+            sH[i] = pair ? swsum32(ch0, h1.x + h1.y) : swsum32(ch0, ch0);
+            hcur = hc2;
+            hnext = hn2;
+        }
+        float tA[H2], tH[H2];
+#pragma unroll
+        for (int i = 0; i < H2; ++i) {
+            tA[i] = (i + H2 < H1) ? swsum16(sA[i], sA[i + H2]) : swsum16(sA[i], sA[i]);
+            tH[i] = (i + H2 < H1) ? swsum16(sH[i], sH[i + H2]) : swsum16(sH[i], sH[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < H2; ++i) {
+            float va = tA[i], vh = tH[i];
+            va += dpp2<0x4E>(va);
+            vh += dpp2<0x4E>(vh);
+            va += dpp2<0x124>(va);
+            vh += dpp2<0x124>(vh);
+            va += dpp2<0x128>(va);
+            vh += dpp2<0x128>(vh);
+            tA[i] = va;
+            tH[i] = vh;
+        }
+        if (ncolw > 0) {
+#pragma unroll
+            for (int i = 0; i < H2; ++i)
+                if (i < ncolw) {
+                    outA[colw + i] = tA[i] + 0.f;                        // (+ 0: prod_At adds its g term, zero here, to every sum)
+                    outH[colw + i] = tH[i] + 0.f;
+                }
+        }
+    };
     // y[CW*wave + KR*rr + r] = sum_c Mat[..][KC*cc + c] * v[KC*cc + c] summed over cc; lanes cc == 0 get the sums
     auto prod_K = [&](const float* v, float (&s)[KR]) {
         float vc[KC];
@@ -466,7 +546,10 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
     // Rows i = tid (+ NT for the lanes that own a second row: with M = NT + 64 that is exactly wave 0).  The two rows of a
     // lane are processed in ONE pass with their loads issued together and their (latency-bound, float64) chains
     // interleaved, instead of two passes back to back -- wave 0 was 520 cycles behind the others at the next barrier.
-    auto row_body = [&](auto nr, bool init, bool do_a, bool do_b) __attribute__((always_inline)) {
+    // chk (with do_a, at a check): the three row norms of compute_residuals and nu = float(lam) are taken while the row is in
+    // registers -- the expressions and casts of res_rows below, rows in the same order
+    float cv[3] = {0.f, 0.f, 0.f};
+    auto row_body = [&](auto nr, bool init, bool do_a, bool do_b, bool chk) __attribute__((always_inline)) {
         constexpr int R = decltype(nr)::value;
         // every LDS operand of the pass is requested up front (one latency, not one per dependent step: left to itself the
         // compiler interleaves reads and waits -- five serial LDS round trips in the one-row path), then the float64 chain
@@ -522,27 +605,42 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
                 nu[i] = (float)(lh + rv * pr);
             }
         }
+        if (chk) {
+            int tid_w = tid;                                           // (the Ruiz weights: a global read through an opaque copy of tid)
+            asm volatile("" : "+v"(tid_w));
+#pragma unroll
+            for (int q = 0; q < R; ++q) {
+                const int i = tid_w + q * NT;
+                const float we = (a.scE && i < m) ? (float)(1.0 / a.scE[mat * m + i]) : 1.f;
+                nu[i] = (float)lmv[q];
+                cv[0] = tmax2(cv[0], fabsf((float)(zt[q] - z[q])) * we);
+                cv[1] = tmax2(cv[1], fabsf((float)zt[q]) * we);
+                cv[2] = tmax2(cv[2], fabsf((float)z[q]) * we);
+            }
+        }
     };
-    auto row_pass = [&](bool init, bool do_a, bool do_b) __attribute__((always_inline)) {
+    auto row_pass = [&](bool init, bool do_a, bool do_b, bool chk = false) __attribute__((always_inline)) {
         if constexpr (M > NT) {
             static_assert(M <= 2 * NT, "at most two rows per lane");
             if (tid + NT < M) {
-                row_body(std::integral_constant<int, 2>{}, init, do_a, do_b);
+                row_body(std::integral_constant<int, 2>{}, init, do_a, do_b, chk);
                 return;
             }
         }
-        if (tid < M) row_body(std::integral_constant<int, 1>{}, init, do_a, do_b);
+        if (tid < M) row_body(std::integral_constant<int, 1>{}, init, do_a, do_b, chk);
     };
 
     __builtin_amdgcn_s_waitcnt(0x0F70);                                // vmcnt(0): A, K and the vectors have landed (see the rho move)
-    unsigned long long t_last = 0, t_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long t_last = 0, t_acc[NSEG] = {};
+    bool k_pend = false;                                               // (DIAG) a K reload is in flight
+    bool diag_on = true;                                               // (DIAG) stamps of the calls outside the solve loop are not counted
     auto stamp = [&](int seg) {
         if constexpr (DIAG) {
             __builtin_amdgcn_sched_barrier(0);
             unsigned long long t;
             asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
             __builtin_amdgcn_sched_barrier(0);
-            if (seg >= 0) t_acc[seg] += t - t_last;
+            if (seg >= 0 && diag_on) t_acc[seg] += t - t_last;
             t_last = t;
         }
     };
@@ -567,10 +665,9 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
 
     // ---- compute_residuals (reluqpth.py:307-318) on the current state (hx = H x valid)
     float scl_p = 0.f, scl_d = 0.f;                                    // residual scales of the last check (eps_rel)
-    auto residuals = [&](float rho_carry, float& o_pri, float& o_dua) -> float {
-        float v[7];
-#pragma unroll
-        for (int e = 0; e < 7; ++e) v[e] = 0.f;
+    // the row part for the call sites without a preceding row pass (mode 2; the final call after max_iter)
+    auto res_rows = [&]() {
+        cv[0] = cv[1] = cv[2] = 0.f;
         // (Ruiz scaling: every term goes back to the caller's space before its norm -- SolveArgs.scE; the weights are read
         //  here, at the check, from an opaque copy of tid: no registers of the solve loop)
         int tid_w = tid;
@@ -578,18 +675,31 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         for (int i = tid_w; i < M; i += NT) {
             const float we = (a.scE && i < m) ? (float)(1.0 / a.scE[mat * m + i]) : 1.f;
             nu[i] = (float)lam64[i];
-            v[0] = tmax2(v[0], fabsf((float)(zt64[i] - z64[i])) * we);
-            v[1] = tmax2(v[1], fabsf((float)zt64[i]) * we);
-            v[2] = tmax2(v[2], fabsf((float)z64[i]) * we);
+            cv[0] = tmax2(cv[0], fabsf((float)(zt64[i] - z64[i])) * we);
+            cv[1] = tmax2(cv[1], fabsf((float)zt64[i]) * we);
+            cv[2] = tmax2(cv[2], fabsf((float)z64[i]) * we);
         }
+    };
+    int rpar = 0;                                                      // check parity: which half of `red` this check uses
+    // cv = the row norms of this thread's rows and nu = float(lam): from row_pass(.., chk) or res_rows()
+    auto residuals = [&](float rho_carry, float& o_pri, float& o_dua) -> float {
+        float v[7];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) v[e] = cv[e];
+#pragma unroll
+        for (int e = 3; e < 7; ++e) v[e] = 0.f;
+        int tid_w = tid;
+        asm volatile("" : "+v"(tid_w));
         __syncthreads();
+        stamp(10);
         if (tid < ND && (tid % SW) >= CW) {                              // padding slots: exact zeros
             dxv[tid] = 0.f;
             hx[tid] = 0.f;
         }
-        prod_At(YES, NO, nu, dxv, false);                              // t3 = A' lam  (dxv is dead here: scratch)
-        prod_At(NO, YES, nu, hx, false);                               // t2 = H x
+        prod_At_chk(nu, dxv, hx);                                      // t3 = A' lam (dxv is dead here: scratch), t2 = H x
+        stamp(11);
         __syncthreads();
+        stamp(13);
         if (tid < ND) {                                                 // padding slots hold zeros
             float wd = 1.f;
             if (a.scD) {
@@ -602,31 +712,49 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
             v[5] = fabsf(t3) * wd;
             v[6] = fabsf(gT[tid]) * wd;
         }
-        // wave max of 7 values + NaN mask (torch max/norm propagate NaN): v_max (IEEE maxNum) on DPP / permlane swaps
+        // Wave max of the 7 values + NaN mask (torch max/norm propagate NaN).  The mask bit of a value is a wave-wide "any lane":
+        // the compare already delivers it as a lane mask, no cross-lane step.  The maxima (v_max, IEEE maxNum: exactly associative
+        // and commutative) are reduced as a reduce-scatter: 8 -> 4 values per lane by permlane32 swaps, 4 -> 2 by permlane16 swaps,
+        // then the four levels inside a row of 16 lanes on two values.  Row r of the wave ends up with values 2r and 2r + 1.
         unsigned nanm = 0;
 #pragma unroll
-        for (int e = 0; e < 7; ++e) nanm |= (v[e] != v[e]) ? (1u << e) : 0u;
-        float nm = __builtin_bit_cast(float, nanm);                    // bit pattern; OR-reduced with integer ops below
-#pragma unroll
-        for (int e = 0; e < 7; ++e) v[e] = wave_max(v[e]);
-        nanm = wave_or(__builtin_bit_cast(unsigned, nm));
-        if (lane == 0) {
-#pragma unroll
-            for (int e = 0; e < 7; ++e) red[wave * 8 + e] = v[e];
-            red[wave * 8 + 7] = __builtin_bit_cast(float, nanm);
+        for (int e = 0; e < 7; ++e) nanm |= (__builtin_amdgcn_ballot_w64(v[e] != v[e]) != 0ull) ? (1u << e) : 0u;
+        float u0, u1;
+        {
+            const float r0 = swmax32(v[0], v[4]), r1 = swmax32(v[1], v[5]), r2 = swmax32(v[2], v[6]), r3 = swmax32(v[3], v[3]);
+            u0 = swmax16(r0, r2);
+            u1 = swmax16(r1, r3);
         }
+        u0 = fmaxf(u0, dpp2<0xB1>(u0));
+        u1 = fmaxf(u1, dpp2<0xB1>(u1));
+        u0 = fmaxf(u0, dpp2<0x4E>(u0));
+        u1 = fmaxf(u1, dpp2<0x4E>(u1));
+        u0 = fmaxf(u0, dpp2<0x141>(u0));
+        u1 = fmaxf(u1, dpp2<0x141>(u1));
+        u0 = fmaxf(u0, dpp2<0x128>(u0));
+        u1 = fmaxf(u1, dpp2<0x128>(u1));
+        // `red` is double-buffered by check parity: the next write of this half is two checks (many barriers) away, so no
+        // barrier is needed behind the reads below
+        float* redp = red + 32 * rpar;
+        rpar ^= 1;
+        if ((lane & 15) == 0) {
+            const int row = lane >> 4;                                   // row 3 holds value 6 and a duplicate: slot 7 takes the mask
+            *(f2*)(redp + wave * 8 + 2 * row) = (f2){u0, row == 3 ? __builtin_bit_cast(float, nanm) : u1};
+        }
+        stamp(14);
         __syncthreads();
+        stamp(15);
         nanm = 0;
 #pragma unroll
-        for (int w = 0; w < NW; ++w) nanm |= __builtin_bit_cast(unsigned, red[w * 8 + 7]);
+        for (int w = 0; w < NW; ++w) nanm |= __builtin_bit_cast(unsigned, redp[w * 8 + 7]);
 #pragma unroll
         for (int e = 0; e < 7; ++e) {
-            float r = red[e];
+            float r = redp[e];
 #pragma unroll
-            for (int w = 1; w < NW; ++w) r = fmaxf(r, red[w * 8 + e]);
+            for (int w = 1; w < NW; ++w) r = fmaxf(r, redp[w * 8 + e]);
             v[e] = ((nanm >> e) & 1u) ? __builtin_nanf("") : r;
         }
-        __syncthreads();
+        stamp(16);
         o_pri = v[0];
         o_dua = v[3];
         scl_p = tmax2(v[1], v[2]);
@@ -648,6 +776,10 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         stamp(1);
         __syncthreads();                                               // B1: d visible
         stamp(2);
+        __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0): the K of a rho move has landed (else: nothing pending)
+        if constexpr (DIAG) {
+            if (k_pend) { stamp(20); k_pend = false; }
+        }
         {
             float s[KR];
             static_assert(KR == 4 || KR == 2, "vectorised x update");
@@ -697,7 +829,10 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
             row_pass(false, true, k < kmax);
             stamp(7);
         } else {
-            row_pass(false, true, false);
+            cv[0] = cv[1] = cv[2] = 0.f;
+            row_pass(false, true, false, true);                        // state k complete, row norms and nu = float(lam) for the check
+            stamp(8);
+            if constexpr (DIAG) t_acc[22] += 1;                        // checks
             const int ri_before = ri;
             rho_est = residuals(rho_est, pri, dua);                    // :220 (Q4: carried estimate)
             rho_est = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rho_est)));
@@ -716,6 +851,7 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
                 tp += (float)a.eps_rel * __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scl_p)));
                 td += (float)a.eps_rel * __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, scl_d)));
             }
+            stamp(18);
             if (pri < tp && dua < td) {
                 converged = true;
                 break;
@@ -742,19 +878,34 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
                     }
                     return;
                 }
-                load_K(ri);
-                set_rho_rows(ri);
-                // wait for the K loads HERE: left pending, the compiler guards every first use of a K register in the solve
-                // loop with its own s_waitcnt vmcnt(N) -- 14 wait instructions per iteration that almost never wait
-                __builtin_amdgcn_s_waitcnt(0x0F70);                    // vmcnt(0)
+                if constexpr (DIAG) { t_acc[23] += 1; k_pend = true; }  // rho moves
+                // The K loads stay in flight: K is first read in prod_K, behind the row pass, B3, the whole A' nu + H x segment
+                // and B1.  The ONE wait sits in front of prod_K (left to the compiler, every first use of a K register in the
+                // solve loop gets its own s_waitcnt vmcnt(N) -- 14 wait instructions per iteration that almost never wait).
+                // The rows' rho_i come from LDS operands only (cT, the ladder): a global read behind the K loads would have to
+                // wait for them too, loads return in order.
+                if constexpr (!KD) load_K(ri);
+                {
+                    int tid_o = tid;
+                    asm volatile("" : "+v"(tid_o));
+                    const float rho = rhoL[ri];                        // = float(rhos[ri])
+                    for (int i = tid_o; i < M; i += NT) {
+                        const float rv = rho * cT[i];
+                        rv32[i] = rv;
+                        inv64[i] = 1.0 / (double)rv;
+                    }
+                }
+                if constexpr (KD) load_K(ri);                          // (consumes its loads on the spot: nothing to overlap)
+                stamp(19);
             }
             if (k < kmax) row_pass(false, false, true);
-            stamp(8);
+            stamp(21);
         }
     }
     if constexpr (DIAG) {
+        diag_on = false;
         if (lane == 0)
-            for (int e = 0; e < 10; ++e) dbg[((size_t)b * 4 + wave) * 10 + e] = (e == 9) ? (unsigned long long)iters : t_acc[e];
+            for (int e = 0; e < NSEG; ++e) dbg[((size_t)b * 4 + wave) * NSEG + e] = (e == NSEG - 1) ? (unsigned long long)iters : t_acc[e];
     }
 
     __syncthreads();
@@ -766,7 +917,10 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         }
         return;
     }
-    if (!converged) rho_est = residuals(rho_est, pri, dua);            // :243 (Q11 fixed: fresh state)
+    if (!converged) {
+        res_rows();
+        rho_est = residuals(rho_est, pri, dua);
+    }            // :243 (Q11 fixed: fresh state)
 
     // objective 1/2 x'Hx + g'x (compute_J :320-322)
     double jp = 0.0;
@@ -1048,24 +1202,32 @@ static hipError_t solve_t(const rqp_handle* h, const SolveArgs& a, hipStream_t s
     }
     if ((h->debug & 2) && !h->k_direct) {   // diagnostic build: per-segment cycle shares of the iteration (synchronous, debug only)
         unsigned long long* dbg = nullptr;
-        const size_t cnt = (size_t)h->B * 4 * 10;
+        const size_t cnt = (size_t)h->B * 4 * NSEG;
         if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
         k_admm_res2<C, true, false><<<h->B, C::NT, lds, s>>>(a, h->Apack, h->Kpack, h->Hpack, dbg, nullptr);
         (void)hipStreamSynchronize(s);
         std::vector<unsigned long long> hbuf(cnt);
         (void)hipMemcpy(hbuf.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
         (void)hipFree(dbg);
-        static const char* names[9] = {"B3 wait", "A'nu+Hx", "B1 wait", "Kd+x", "A dx", "B2 wait", "-", "rows", "check"};
+        static const char* names[22] = {"B3 wait", "A'nu+Hx", "B1 wait", "Kd+x", "A dx", "B2 wait", "-", "rows",
+                                        "rows(a)", "res rows", "R1 wait", "A'lam", "Hx", "R2 wait", "norms+reduce", "R3 wait", "combine",
+                                        "R4 wait", "decision", "K issue+rho rows", "K wait", "rows(b)"};
         for (int w = 0; w < 4; ++w) {
-            double tot[9] = {0}, its = 0;
-            for (int b = 0; b < h->B; ++b) {
-                for (int e = 0; e < 9; ++e) tot[e] += (double)hbuf[((size_t)b * 4 + w) * 10 + e];
-                its += (double)hbuf[((size_t)b * 4 + w) * 10 + 9];
-            }
+            double tot[NSEG] = {0};
+            for (int b = 0; b < h->B; ++b)
+                for (int e = 0; e < NSEG; ++e) tot[e] += (double)hbuf[((size_t)b * 4 + w) * NSEG + e];
+            const double its = tot[NSEG - 1], chk = tot[22] > 0 ? tot[22] : 1.0;
+            // the segments of an ordinary iteration, with the whole check as one figure ("check"), per iteration ...
             fprintf(stderr, "[rqp diag] wave %d cycles/iteration:", w);
-            double sum = 0;
-            for (int e = 0; e < 9; ++e) { fprintf(stderr, " %s=%.0f", names[e], tot[e] / its); sum += tot[e] / its; }
-            fprintf(stderr, " | total=%.0f\n", sum);
+            double sum = 0, csum = 0;
+            for (int e = 8; e < 22; ++e) csum += tot[e];
+            for (int e = 0; e < 8; ++e) { fprintf(stderr, " %s=%.0f", names[e], tot[e] / its); sum += tot[e] / its; }
+            fprintf(stderr, " check=%.0f | total=%.0f\n", csum / its, sum + csum / its);
+            // ... and the check taken apart, per check ("K issue+rho rows" and "K wait" occur only at a rho move)
+            fprintf(stderr, "[rqp diag] wave %d cycles/check:", w);
+            for (int e = 8; e < 22; ++e) fprintf(stderr, " %s=%.0f", names[e], tot[e] / chk);
+            fprintf(stderr, " | total=%.0f ; checks/instance=%.2f moves/instance=%.2f moves/check=%.3f\n", csum / chk, tot[22] / h->B,
+                    tot[23] / h->B, tot[23] / chk);
         }
         return hipGetLastError();
     }
