@@ -27,6 +27,22 @@ hipError_t rqp_raise_lds_limit(const void* fn, size_t bytes) {
     return e;
 }
 
+std::vector<double> rqp_diag_run(hipStream_t s, size_t groups, int waves, int slots, const std::function<void(unsigned long long*)>& launch) {
+    unsigned long long* ticks = nullptr;
+    const size_t cnt = groups * waves * slots;
+    if (hipMalloc((void**)&ticks, cnt * 8) != hipSuccess) return {};
+    launch(ticks);
+    (void)hipStreamSynchronize(s);
+    std::vector<unsigned long long> hb(cnt);
+    (void)hipMemcpy(hb.data(), ticks, cnt * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(ticks);
+    std::vector<double> tot((size_t)waves * slots, 0.0);
+    for (int w = 0; w < waves; ++w)
+        for (size_t g = 0; g < groups; ++g)
+            for (int e = 0; e < slots; ++e) tot[(size_t)w * slots + e] += (double)hb[(g * waves + w) * slots + e];
+    return tot;
+}
+
 #define RQP_VERSION "rqp-hip 0.3 gfx950"
 
 namespace {
@@ -92,27 +108,45 @@ int argmin_abs(const std::vector<double>& r, double v) {   // np.argmin(np.abs(r
     return best;
 }
 
+// The ADMM kernels, by rqp_kernel_id.
+const rqp_kernel_desc rqp_kernels[RQP_K_COUNT] = {
+    /* RQP_K_GENERIC */ {"generic", rqp_launch_solve_generic, nullptr, nullptr, nullptr},
+    /* RQP_K_RES2    */ {"resident2", rqp_launch_solve_res2, nullptr, nullptr, nullptr},
+    /* RQP_K_RES64   */ {"resident64", rqp_launch_solve_res64, nullptr, nullptr, nullptr},
+    /* RQP_K_WAVE    */ {"wave", rqp_launch_solve_wave, nullptr, nullptr, nullptr},
+    /* RQP_K_MFMA    */ {"mfma", rqp_launch_solve_mfma, rqp_mfma_img_elems, rqp_prepare_mfma, rqp_launch_pack_mfma},
+    /* RQP_K_MFMA16  */ {"mfma16", rqp_launch_solve_mfma16, rqp_mfma16_img_elems, rqp_prepare_mfma16, rqp_launch_pack_mfma16},
+    /* RQP_K_MFMAL   */ {"mfmal", rqp_launch_solve_mfmal, rqp_mfmal_img_elems, rqp_prepare_mfmal, rqp_launch_pack_mfmal},
+    /* RQP_K_MFMAD   */ {"mfmad", rqp_launch_solve_mfmad, rqp_mfmad_img_elems, rqp_prepare_mfmad, rqp_launch_pack_mfmad},
+};
+
+// solve kernel: shared-(H, A) batches in 16-instance tiles on the matrix pipe, with an operand image (W1img); solve() only
+bool tile_kernel(const rqp_handle* h) { return rqp_kernels[h->solve_kernel].pack != nullptr; }
+// ... whose operands stream from L2 (slots grouped by starting rho index)
+bool streams_operands(const rqp_handle* h) { return h->solve_kernel == RQP_K_MFMAL || h->solve_kernel == RQP_K_MFMAD; }
+// k_admm_res2 runs on this handle -- as its solve kernel, or behind a tile kernel -- and so the handle keeps its register images
+bool uses_res2(const rqp_handle* h) { return h->aux_kernel == RQP_K_RES2; }
+
+// Handle-owned device memory: every allocation is recorded by the field that holds it; free_ws needs no list of its own.
+template <class T>
+hipError_t dev_alloc(rqp_handle* h, T** field, size_t bytes) {
+    const hipError_t e = hipMalloc((void**)field, bytes);
+    if (e == hipSuccess) h->owned.push_back((void**)field);
+    return e;
+}
+
 void free_ws(rqp_handle* h) {
-    void** ptrs[] = {&h->Ht, &h->A, &h->At, &h->K, &h->g, &h->l, &h->u, &h->c, (void**)&h->G,
-                     (void**)&h->x, (void**)&h->z, (void**)&h->lam, (void**)&h->rho_ind, (void**)&h->rhos_d,
-                     (void**)&h->fscratch, (void**)&h->Apack, (void**)&h->Kpack, (void**)&h->Hpack, (void**)&h->Kscale, (void**)&h->W1img, (void**)&h->queue,
-                     (void**)&h->flag_d, (void**)&h->order_d, (void**)&h->last_iter_d, (void**)&h->cont_iter_d, (void**)&h->cont_rho_d,
-                     (void**)&h->Dsc, (void**)&h->Esc, (void**)&h->csc, (void**)&h->wbase_d, (void**)&h->ax_d, (void**)&h->cstat_d, (void**)&h->key_d,
-                     (void**)&h->ncont_d, (void**)&h->polish_G, (void**)&h->polish_Minv, (void**)&h->polish_rho,
-                     (void**)&h->polish_status, (void**)&h->polish_act, (void**)&h->polish_flag, (void**)&h->polish_st_in,
-                     (void**)&h->polish_res_in, &h->adj_Ht, &h->adj_A, (void**)&h->adj_G_own, (void**)&h->adj_Minv_own,
-                     (void**)&h->adj_rho, (void**)&h->adj_flag, (void**)&h->adj_act, (void**)&h->adj_rows,
-                     (void**)&h->sens_idx, (void**)&h->sens_pos, (void**)&h->sens_na, (void**)&h->sens_ws};
     // hipFree is one of the calls that invalidate a stream capture in progress (global / thread-local capture modes).  A handle
     // may be destroyed while this thread captures something else (a Python finaliser, an explicit `del`): free under the
     // relaxed mode, which exists for exactly this.
     hipStreamCaptureMode cmode = hipStreamCaptureModeRelaxed;
     const bool swapped = hipThreadExchangeStreamCaptureMode(&cmode) == hipSuccess;
-    for (void** p : ptrs) {
-        if (*p) (void)hipFree(*p);
+    for (void** p : h->owned) {
+        (void)hipFree(*p);
         *p = nullptr;
     }
-    h->adj_G = h->adj_Minv = nullptr;             // (the owned ones are freed above; otherwise polish's)
+    h->owned.clear();
+    h->adj_G = h->adj_Minv = nullptr;             // (aliases of polish's buffers when not in `owned`)
     if (h->ncont_h) (void)hipHostFree(h->ncont_h);
     if (swapped) (void)hipThreadExchangeStreamCaptureMode(&cmode);
     h->ncont_h = nullptr;
@@ -121,21 +155,12 @@ void free_ws(rqp_handle* h) {
     h->kpack_direct = false;
     h->is_setup = false;
     h->order_valid = false;
-    h->resident = false;
-    h->resident64 = false;
-    h->use_mfma = false;
-    h->use_wave = false;
-    h->kernel_name = "generic";
+    h->solve_kernel = h->aux_kernel = RQP_K_GENERIC;
 }
 
+// mode 0 (the cont = 2 passes of a windowed handle included) runs on the solve kernel, iterate / residuals on the auxiliary one
 hipError_t launch_solve(const rqp_handle* h, const SolveArgs& a, hipStream_t s) {
-    if (h->use_mfma && a.mode == 0)
-        return h->mfmad ? rqp_launch_solve_mfmad(h, a, s)
-                        : (h->mfmal ? rqp_launch_solve_mfmal(h, a, s) : (h->mfma16 ? rqp_launch_solve_mfma16(h, a, s) : rqp_launch_solve_mfma(h, a, s)));
-    if (h->use_wave && a.mode == 0) return rqp_launch_solve_wave(h, a, s);
-    if (h->resident) return rqp_launch_solve_res2(h, a, s);
-    if (h->resident64) return rqp_launch_solve_res64(h, a, s);
-    return rqp_launch_solve_generic(h, a, s);
+    return rqp_kernels[a.mode == 0 ? h->solve_kernel : h->aux_kernel].solve(h, a, s);
 }
 
 SolveArgs make_solve_args(const rqp_handle* h) {
@@ -197,38 +222,43 @@ SetupArgs make_setup_args(const rqp_handle* h, const void* H, const void* g, con
 
 // Kernel selection (rqp_dims.kernel; AUTO = measured crossovers).  Pure function of the handle: no environment.
 int select_kernels(rqp_handle* h) {
+    h->solve_kernel = h->aux_kernel = RQP_K_GENERIC;
+    const bool res2_fits = rqp_res2_fits(h), res64_fits = rqp_res64_fits(h), wave_fits = rqp_wave_fits(h);
+    const bool mfma_fits = rqp_mfma_fits(h), mfmal_fits = rqp_mfmal_fits(h), mfmad_fits = rqp_mfmad_fits(h);
+    const bool f16 = h->dims.tile_dtype == RQP_TILE_F16, bf16 = h->dims.tile_dtype == RQP_TILE_BF16;
+    // ---- the request, after the tile formats' say
     int req = h->dims.kernel;
-    if (h->dims.tile_dtype == RQP_TILE_F16) {     // the fp16 K tile lives in the register-resident kernel; the MFMA kernel takes
+    if (f16) {                                    // the fp16 K tile lives in the register-resident kernel; the MFMA kernel takes
                                                   // the same rounded K into its float32 operand image (k_pack_mfma)
-        const bool mfma_ok = rqp_mfma_fits(h) && rqp_res2_fits(h);
-        if (req == RQP_KERNEL_AUTO && rqp_res2_fits(h) && !(mfma_ok && h->B >= 2048 && (h->n > 56 || h->m > 128))) req = RQP_KERNEL_RESIDENT;
+        const bool mfma_ok = mfma_fits && res2_fits;
+        if (req == RQP_KERNEL_AUTO && res2_fits && !(mfma_ok && h->B >= 2048 && (h->n > 56 || h->m > 128))) req = RQP_KERNEL_RESIDENT;
         if (req != RQP_KERNEL_RESIDENT && !((req == RQP_KERNEL_MFMA || req == RQP_KERNEL_AUTO) && mfma_ok))
             return fail_unsupported(h, "tile_dtype = f16 needs the resident kernel (float32, n <= 104, m <= 320) or the MFMA kernel");
     }
-    h->resident = h->resident64 = h->use_wave = h->use_mfma = h->mfma16 = h->mfmal = h->mfmad = false;
-    h->kernel_name = "generic";
-    if (h->dims.tile_dtype == RQP_TILE_BF16) {     // the bf16-plane tile exists in the MFMA kernel only: an explicit request for it
-        if (!rqp_mfma_fits(h) || (req != RQP_KERNEL_AUTO && req != RQP_KERNEL_MFMA))
+    if (bf16) {                                   // the bf16-plane tile exists in the MFMA kernel only: an explicit request for it
+        if (!mfma_fits || (req != RQP_KERNEL_AUTO && req != RQP_KERNEL_MFMA))
             return fail_unsupported(h, "tile_dtype = bf16 needs the MFMA kernel: float32, shared (H, A), n <= 80, m <= 320");
         req = RQP_KERNEL_MFMA;
-        h->mfma16 = true;
     }
+    // ---- the solve kernel
+    rqp_kernel_id k = RQP_K_GENERIC;
     switch (req) {
         case RQP_KERNEL_GENERIC:
             break;
         case RQP_KERNEL_RESIDENT:
-            if (rqp_res2_fits(h)) h->resident = true;
-            else if (rqp_res64_fits(h)) h->resident64 = true;
+            if (res2_fits) k = RQP_K_RES2;
+            else if (res64_fits) k = RQP_K_RES64;
             else return fail_unsupported(h, "kernel=resident: needs n <= 104, m <= 320");
             break;
         case RQP_KERNEL_WAVE:
-            if (!rqp_wave_fits(h)) return fail_unsupported(h, "kernel=wave: needs n <= 32, m <= 64 (float32 also n <= 32, m <= 128 and 56 < n <= 64, m <= 128)");
-            h->use_wave = true;
+            if (!wave_fits) return fail_unsupported(h, "kernel=wave: needs n <= 32, m <= 64 (float32 also n <= 32, m <= 128 and 56 < n <= 64, m <= 128)");
+            k = RQP_K_WAVE;
             break;
         case RQP_KERNEL_MFMA:
-            if (rqp_mfma_fits(h)) h->use_mfma = true;                         // operands resident in registers
-            else if (rqp_mfmal_fits(h) && !h->mfma16) h->use_mfma = h->mfmal = true;   // operands streamed from L2 (rqp_mfmal.hip)
-            else if (rqp_mfmad_fits(h) && !h->mfma16) h->use_mfma = h->mfmad = true;   // float64 MFMA, streamed operands (rqp_mfmad.hip)
+            if (mfma_fits && bf16) k = RQP_K_MFMA16;                          // (bf16 was refused above where mfma_fits does not hold)
+            else if (mfma_fits) k = RQP_K_MFMA;                               // operands resident in registers
+            else if (mfmal_fits) k = RQP_K_MFMAL;                             // operands streamed from L2 (rqp_mfmal.hip)
+            else if (mfmad_fits) k = RQP_K_MFMAD;                             // float64 MFMA, streamed operands (rqp_mfmad.hip)
             else return fail_unsupported(h, "kernel=mfma: needs shared (H, A) and float32 with n <= 320, m <= 640 (bf16 tile: n <= 80, m <= 320) "
                                             "or float64 with n <= 160, m <= 320");
             break;
@@ -244,44 +274,43 @@ int select_kernels(rqp_handle* h) {
             // leaves at the first check where one holds, like the oracle; the other kernels would run it to max_iter first)
             if (h->st.check_infeasibility)
                 break;
-            if (rqp_mfma_fits(h) && mfma_pays)
-                h->use_mfma = true;
-            else if (rqp_mfmal_fits(h) && !rqp_res2_fits(h) && !rqp_wave_fits(h))
-                h->use_mfma = h->mfmal = true;   // beyond every resident tile (the sparse linear-MPC form): 16-instance MFMA tiles with
+            if (mfma_fits && mfma_pays)
+                k = RQP_K_MFMA;
+            else if (mfmal_fits && !res2_fits && !wave_fits)
+                k = RQP_K_MFMAL;                 // beyond every resident tile (the sparse linear-MPC form): 16-instance MFMA tiles with
                                                  // streamed operands instead of the streaming kernel's 2 MB of matrices per instance-iteration
                                                  // (any batch: ONE instance solves in 1.0 ms against 2.8 ms, tools/mfmal_check.py 1)
-            else if (rqp_mfmad_fits(h) && ((mfma_pays && h->B >= 3072) || (!rqp_res64_fits(h) && !rqp_wave_fits(h))))
-                h->use_mfma = h->mfmad = true;   // float64 shared batches: 16-instance tiles on v_mfma_f64_16x16x4_f64 from ~3k instances
+            else if (mfmad_fits && ((mfma_pays && h->B >= 3072) || (!res64_fits && !wave_fits)))
+                k = RQP_K_MFMAD;                 // float64 shared batches: 16-instance tiles on v_mfma_f64_16x16x4_f64 from ~3k instances
                                                  // (measured on the condensed-MPC shape: 4096 -> 1.5x the float64 resident kernel; at
                                                  // 2048 one resident instance per CU still wins), or whenever no resident kernel fits
-            else if (rqp_wave_fits(h))       // small problems: one wavefront per instance
-                h->use_wave = true;
-            else if (rqp_res2_fits(h))
-                h->resident = true;
-            else if (rqp_res64_fits(h))      // float64 (the reference's default precision) at the headline sizes
-                h->resident64 = true;
+            else if (wave_fits)                  // small problems: one wavefront per instance
+                k = RQP_K_WAVE;
+            else if (res2_fits)
+                k = RQP_K_RES2;
+            else if (res64_fits)                 // float64 (the reference's default precision) at the headline sizes
+                k = RQP_K_RES64;
         }
     }
-    // iterate / residuals modes of an MFMA or wave handle run on the resident tile when one fits, else on the streaming kernel
-    if (h->use_mfma && rqp_res2_fits(h)) h->resident = true;
-    if (h->dims.tile_dtype == RQP_TILE_F16 && !h->resident) return fail_unsupported(h, "tile_dtype = f16 needs the resident kernel");
+    h->solve_kernel = k;
+    // ---- the auxiliary kernel: the resident kernels run every mode themselves; iterate / residuals and the hand-off of a TILE-kernel
+    // handle run on the float32 resident tile when one fits; those of every other handle -- a wave handle too -- on the streaming kernel
+    if (k == RQP_K_RES2 || k == RQP_K_RES64) h->aux_kernel = k;
+    else if (tile_kernel(h) && res2_fits) h->aux_kernel = RQP_K_RES2;
+    if (f16 && !uses_res2(h)) return fail_unsupported(h, "tile_dtype = f16 needs the resident kernel");
+    // ---- what follows from the two
     // RQP_FLAG_LOW_MEMORY: the float32 resident kernel reads K from the row-major table (no effect on the other kernels, which
     // have no packed copy of it; the fp16 tile IS the smaller copy)
-    h->k_direct = (h->dims.flags & RQP_FLAG_LOW_MEMORY) && h->resident && h->dims.tile_dtype != RQP_TILE_F16;
+    h->k_direct = (h->dims.flags & RQP_FLAG_LOW_MEMORY) && uses_res2(h) && !f16;
     // rho-ladder window (rqp_common.h): batches of per-instance matrices whose solve kernel runs the exit-and-continue protocol
     // (resident float32 / float64 tiles, one-wavefront kernel, streaming kernel).  Not with check_infeasibility (its certificate pass reads K at the final index)
     // and not on request (RQP_FLAG_FULL_LADDER: rqp_solve then never synchronises the host, e.g. for graph capture).
-    h->kwin = h->nrho;
     h->windowed = !h->dims.shared_mats && h->nmat >= 32 && h->nrho > RQP_WINDOW && !(h->dims.flags & RQP_FLAG_FULL_LADDER) &&
-                  !h->st.check_infeasibility && !h->use_mfma;
-    if (h->windowed) h->kwin = RQP_WINDOW;
+                  !h->st.check_infeasibility && !tile_kernel(h);
+    h->kwin = h->windowed ? RQP_WINDOW : h->nrho;
     // (rqp_common.h; not on a handle set up for polishing, which reads the row-major A after every solve)
-    h->borrow_A = h->windowed && h->resident && h->st.scaling <= 0 && h->ldn == h->n && !h->polish_reserved;
-    h->kpack_direct = h->windowed && h->resident && !h->k_direct && h->dims.tile_dtype != RQP_TILE_F16;
-    if (h->use_mfma) h->kernel_name = h->mfmad ? "mfmad" : (h->mfmal ? "mfmal" : (h->mfma16 ? "mfma16" : "mfma"));
-    else if (h->use_wave) h->kernel_name = "wave";
-    else if (h->resident) h->kernel_name = "resident2";
-    else if (h->resident64) h->kernel_name = "resident64";
+    h->borrow_A = h->windowed && uses_res2(h) && h->st.scaling <= 0 && h->ldn == h->n && !h->polish_reserved;
+    h->kpack_direct = h->windowed && uses_res2(h) && !h->k_direct && !f16;
     return RQP_OK;
 }
 
@@ -298,13 +327,13 @@ int build_matrices(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
     HIP_TRY(h, rqp_launch_pack_mats(h, a, s));
     if (h->st.scaling > 0) HIP_TRY(h, rqp_launch_ruiz(h, s));       // Ht, A, At scaled in place; D, E, c kept for the boundary
     if (a.A) HIP_TRY(h, rqp_launch_gram(h, a, s));                  // (NULL: a handle without a copy of A that keeps its A -- G = A'cA stands)
-    if (h->resident && !h->Apack) {                                 // (before the factor launch: kpack_direct writes Kpack there)
+    if (uses_res2(h) && !h->Apack) {                                // (before the factor launch: kpack_direct writes Kpack there)
         size_t ae, ke, he;
         rqp_res2_pack_elems(h, &ae, &ke, &he);
-        HIP_TRY(h, hipMalloc((void**)&h->Apack, ae * sizeof(float)));
-        if (ke) HIP_TRY(h, hipMalloc((void**)&h->Kpack, ke * sizeof(float)));   // (none with RQP_FLAG_LOW_MEMORY)
-        HIP_TRY(h, hipMalloc((void**)&h->Hpack, he * sizeof(float)));
-        if (h->dims.tile_dtype == RQP_TILE_F16) HIP_TRY(h, hipMalloc((void**)&h->Kscale, (size_t)h->nmat * h->nrho * sizeof(float)));
+        HIP_TRY(h, dev_alloc(h, &h->Apack, ae * sizeof(float)));
+        if (ke) HIP_TRY(h, dev_alloc(h, &h->Kpack, ke * sizeof(float)));   // (none with RQP_FLAG_LOW_MEMORY)
+        HIP_TRY(h, dev_alloc(h, &h->Hpack, he * sizeof(float)));
+        if (h->dims.tile_dtype == RQP_TILE_F16) HIP_TRY(h, dev_alloc(h, &h->Kscale, (size_t)h->nmat * h->nrho * sizeof(float)));
         HIP_TRY(h, rqp_prepare_res2(h));
     }
     {
@@ -312,16 +341,204 @@ int build_matrices(rqp_handle* h, const SetupArgs& a, hipStream_t s) {
         set_kp_image(h, f);
         HIP_TRY(h, rqp_launch_factor(h, f, s));
     }
-    if (h->resident) HIP_TRY(h, rqp_launch_pack_res2(h, a.A, nullptr, nullptr, s));
-    if (h->resident64) HIP_TRY(h, rqp_prepare_res64(h));
-    if (h->use_mfma) {
+    if (uses_res2(h)) HIP_TRY(h, rqp_launch_pack_res2(h, a.A, nullptr, nullptr, s));
+    if (h->solve_kernel == RQP_K_RES64) HIP_TRY(h, rqp_prepare_res64(h));
+    if (tile_kernel(h)) {
+        const rqp_kernel_desc& k = rqp_kernels[h->solve_kernel];
         if (!h->W1img) {
-            const size_t elems = h->mfmad ? rqp_mfmad_img_elems(h) : (h->mfmal ? rqp_mfmal_img_elems(h) : (h->mfma16 ? rqp_mfma16_img_elems(h) : rqp_mfma_img_elems(h)));
-            HIP_TRY(h, hipMalloc((void**)&h->W1img, elems * sizeof(float)));
-            HIP_TRY(h, hipMalloc((void**)&h->queue, sizeof(int)));
-            HIP_TRY(h, h->mfmad ? rqp_prepare_mfmad(h) : (h->mfmal ? rqp_prepare_mfmal(h) : (h->mfma16 ? rqp_prepare_mfma16(h) : rqp_prepare_mfma(h))));
+            HIP_TRY(h, dev_alloc(h, &h->W1img, k.img_elems(h) * sizeof(float)));
+            HIP_TRY(h, dev_alloc(h, &h->queue, sizeof(int)));
+            HIP_TRY(h, k.prepare(h));
         }
-        HIP_TRY(h, h->mfmad ? rqp_launch_pack_mfmad(h, s) : (h->mfmal ? rqp_launch_pack_mfmal(h, s) : (h->mfma16 ? rqp_launch_pack_mfma16(h, s) : rqp_launch_pack_mfma(h, s))));
+        HIP_TRY(h, k.pack(h, s));
+    }
+    return RQP_OK;
+}
+
+// ---- rqp_setup's workspace, in steps.  Each returns at its first failure; rqp_setup then releases everything (free_ws).
+
+// matrices, vectors, ADMM state, the rho ladder, and what the solve kernel's launch order needs
+int alloc_core(rqp_handle* h, hipStream_t s) {
+    const size_t n = h->n, m = h->m, B = h->B, nm = h->nmat, e = h->esz;
+    HIP_TRY(h, dev_alloc(h, &h->Ht, nm * n * h->ldn * e));
+    if (!h->borrow_A) HIP_TRY(h, dev_alloc(h, &h->A, nm * m * h->ldn * e));     // (rqp_common.h: borrow_A)
+    // A' (the streaming kernel's A dx operand and the wavefront kernel's column role): not on a windowed resident handle, whose
+    // solve / iterate / residuals all run on k_admm_res2 / k_admm_res64 (neither reads A') and which refuses the certificate pass
+    // (float32: 0.5 GB and 0.4 ms at B = 4096; float64: 1 GB and 1 ms)
+    const bool resident_solve = h->solve_kernel == RQP_K_RES2 || h->solve_kernel == RQP_K_RES64;
+    if (!(h->windowed && resident_solve)) HIP_TRY(h, dev_alloc(h, &h->At, nm * n * h->ldm * e));
+    if (!h->kpack_direct) {   // (+ a zeroed tail: the low-memory K load of the resident kernel reads up to one vector past a row's end)
+        const size_t kb = nm * h->kwin * n * h->ldn * e;
+        HIP_TRY(h, dev_alloc(h, &h->K, kb + 256));
+        HIP_TRY(h, hipMemsetAsync((char*)h->K + kb, 0, 256, s));
+    }
+    HIP_TRY(h, dev_alloc(h, &h->g, B * n * e));
+    for (void** v : {&h->l, &h->u, &h->c}) HIP_TRY(h, dev_alloc(h, v, B * m * e));
+    HIP_TRY(h, dev_alloc(h, &h->G, nm * n * n * sizeof(double)));
+    HIP_TRY(h, dev_alloc(h, &h->x, B * n * sizeof(double)));
+    for (double** v : {&h->z, &h->lam}) HIP_TRY(h, dev_alloc(h, v, B * m * sizeof(double)));
+    HIP_TRY(h, dev_alloc(h, &h->rho_ind, B * sizeof(int32_t)));
+    HIP_TRY(h, dev_alloc(h, &h->rhos_d, h->nrho * sizeof(double)));
+    HIP_TRY(h, hipMemcpyAsync(h->rhos_d, h->rhos.data(), h->nrho * sizeof(double), hipMemcpyHostToDevice, s));
+    const size_t lds_need = (n * n + 2 * n) * sizeof(double);
+    if (lds_need > 160 * 1024 - 512) {   // factor scratch in global memory
+        h->fscratch_elems = nm * h->kwin * n * n;
+        HIP_TRY(h, dev_alloc(h, &h->fscratch, h->fscratch_elems * sizeof(double)));
+    }
+    HIP_TRY(h, dev_alloc(h, &h->flag_d, sizeof(int32_t)));
+    if (h->st.scaling > 0) {
+        HIP_TRY(h, dev_alloc(h, &h->Dsc, nm * n * sizeof(double)));
+        HIP_TRY(h, dev_alloc(h, &h->Esc, nm * m * sizeof(double)));
+        HIP_TRY(h, dev_alloc(h, &h->csc, nm * sizeof(double)));
+    }
+    if (streams_operands(h) && h->B > 16)          // slot order of the streamed-operand MFMA kernels (grouped by starting rho index)
+        HIP_TRY(h, dev_alloc(h, &h->order_d, B * sizeof(int32_t)));
+    if (h->solve_kernel == RQP_K_MFMAL && h->B > 16) {   // regrouped cold solve (rqp_mfmal.hip): exact state of the instances between its two launches
+        HIP_TRY(h, dev_alloc(h, &h->ax_d, B * m * sizeof(double)));
+        HIP_TRY(h, dev_alloc(h, &h->cont_rho_d, B * sizeof(double)));
+        HIP_TRY(h, dev_alloc(h, &h->key_d, B * sizeof(int32_t)));
+    }
+    if (!tile_kernel(h) && h->B >= (h->solve_kernel == RQP_K_RES64 ? 2 : 4) * h->ncu) {   // dispatch order (see rqp_common.h): batches that outlast one wave of workgroups
+        HIP_TRY(h, dev_alloc(h, &h->order_d, B * sizeof(int32_t)));
+        HIP_TRY(h, dev_alloc(h, &h->last_iter_d, B * sizeof(int32_t)));
+    }
+    return RQP_OK;
+}
+
+// rho-ladder window: every window starts around rho_ind0; the exit-and-continue state of the instances
+int alloc_window(rqp_handle* h, hipStream_t s) {
+    const size_t m = h->m, B = h->B, nm = h->nmat;
+    const int w0 = std::min(std::max(h->rho_ind0 - 1, 0), h->nrho - h->kwin);
+    HIP_TRY(h, dev_alloc(h, &h->wbase_d, nm * sizeof(int32_t)));
+    HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->wbase_d, w0, nm, s));
+    HIP_TRY(h, dev_alloc(h, &h->ax_d, B * m * sizeof(double)));
+    HIP_TRY(h, dev_alloc(h, &h->cstat_d, B * sizeof(int32_t)));
+    HIP_TRY(h, hipMemsetAsync(h->cstat_d, 0, B * sizeof(int32_t), s));
+    HIP_TRY(h, dev_alloc(h, &h->ncont_d, 2 * sizeof(int32_t)));
+    HIP_TRY(h, hipHostMalloc((void**)&h->ncont_h, sizeof(int32_t), hipHostMallocDefault));
+    HIP_TRY(h, dev_alloc(h, &h->cont_iter_d, B * sizeof(int32_t)));
+    HIP_TRY(h, dev_alloc(h, &h->cont_rho_d, B * sizeof(double)));
+    return RQP_OK;
+}
+
+// The factor kernels read rho from the ladder array: a one-element "ladder" holding 1 / delta.  The value is copied from this
+// stack frame, so the stream is drained before returning.
+int alloc_inv_delta(rqp_handle* h, double** field, double delta, hipStream_t s) {
+    const double idel = 1.0 / delta;
+    HIP_TRY(h, dev_alloc(h, field, sizeof(double)));
+    HIP_TRY(h, hipMemcpyAsync(*field, &idel, sizeof(double), hipMemcpyHostToDevice, s));
+    HIP_TRY(h, hipStreamSynchronize(s));
+    return RQP_OK;
+}
+
+// solution polishing (rqp_polish.hip): chunked float64 workspace, per-instance results
+int alloc_polish(rqp_handle* h, hipStream_t s) {
+    const size_t n = h->n, m = h->m, B = h->B;
+    if (rqp_polish_lds_bytes(h) > 160 * 1024)
+        return fail_unsupported(h, "rqp_setup: polish needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
+    h->polish_chunk = rqp_polish_chunk(h);
+    const size_t pc = h->polish_chunk;
+    HIP_TRY(h, dev_alloc(h, &h->polish_G, pc * n * n * sizeof(double)));
+    HIP_TRY(h, dev_alloc(h, &h->polish_Minv, pc * n * h->ldn * sizeof(double)));
+    if (const int rc = alloc_inv_delta(h, &h->polish_rho, h->polish_delta, s)) return rc;
+    HIP_TRY(h, dev_alloc(h, &h->polish_status, B * sizeof(int32_t)));
+    HIP_TRY(h, hipMemsetAsync(h->polish_status, 0, B * sizeof(int32_t), s));
+    HIP_TRY(h, dev_alloc(h, &h->polish_act, B * m));
+    HIP_TRY(h, hipMemsetAsync(h->polish_act, 0, B * m, s));
+    HIP_TRY(h, dev_alloc(h, &h->polish_flag, B * sizeof(int32_t)));
+    HIP_TRY(h, dev_alloc(h, &h->polish_st_in, B * sizeof(int32_t)));
+    HIP_TRY(h, dev_alloc(h, &h->polish_res_in, 3 * B * sizeof(double)));
+    return RQP_OK;
+}
+
+// adjoint (rqp_adjoint.hip) and forward sensitivities (rqp_sens.hip): packed caller matrices, G_a and M^-1 per chunk
+int alloc_adjoint(rqp_handle* h, hipStream_t s) {
+    const size_t n = h->n, m = h->m, B = h->B, e = h->esz;
+    if (h->adj_reserved && rqp_adjoint_lds_bytes(h) > 160 * 1024)
+        return fail_unsupported(h, "rqp_setup: the adjoint needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
+    if (h->sens_reserved && rqp_sens_lds_bytes(h) > 160 * 1024)
+        return fail_unsupported(h, "rqp_setup: the sensitivities need 384 ceil16(n) + 2 KB of LDS, above 160 KB");
+    h->adj_chunk = rqp_polish_chunk(h);
+    const size_t pc = h->adj_chunk, pm = h->dims.shared_mats ? 1 : pc;
+    HIP_TRY(h, dev_alloc(h, &h->adj_Ht, pm * n * h->ldn * e));
+    HIP_TRY(h, dev_alloc(h, &h->adj_A, pm * m * h->ldn * e));
+    if (h->polish_reserved) {               // (same chunk rule: polish's buffers hold one chunk of either) aliases, not allocations
+        h->adj_G = h->polish_G;
+        h->adj_Minv = h->polish_Minv;
+    } else {
+        HIP_TRY(h, dev_alloc(h, &h->adj_G, pc * n * n * sizeof(double)));
+        HIP_TRY(h, dev_alloc(h, &h->adj_Minv, pc * n * h->ldn * sizeof(double)));
+    }
+    if (const int rc = alloc_inv_delta(h, &h->adj_rho, h->adj_delta, s)) return rc;
+    HIP_TRY(h, dev_alloc(h, &h->adj_flag, B * sizeof(int32_t)));
+    HIP_TRY(h, dev_alloc(h, &h->adj_act, B * m));
+    if (h->adj_reserved)                    // per-instance rows of the matrix gradients
+        HIP_TRY(h, dev_alloc(h, &h->adj_rows, B * (2 * n + 2 * m) * sizeof(double)));
+    if (h->sens_reserved) {                 // active-row lists, one chunk of direction blocks
+        for (int32_t** v : {&h->sens_idx, &h->sens_pos}) HIP_TRY(h, dev_alloc(h, v, B * m * sizeof(int32_t)));
+        HIP_TRY(h, dev_alloc(h, &h->sens_na, B * sizeof(int32_t)));
+        HIP_TRY(h, dev_alloc(h, &h->sens_ws, pc * rqp_sens_ws_doubles(h) * sizeof(double)));
+    }
+    return RQP_OK;
+}
+
+// straggler hand-off (SolveArgs) of a tile kernel to k_admm_res2: one tile per CU at most
+int alloc_handoff(rqp_handle* h) {
+    h->handoff_cols = 0;
+    if (!(tile_kernel(h) && uses_res2(h) && (h->B + 15) / 16 <= h->ncu)) return RQP_OK;
+    HIP_TRY(h, dev_alloc(h, &h->cont_iter_d, (size_t)h->B * sizeof(int32_t)));
+    if (!h->cont_rho_d)                     // (k_admm_mfmal's regrouped cold solve has one already; a solve uses it for one of the two)
+        HIP_TRY(h, dev_alloc(h, &h->cont_rho_d, (size_t)h->B * sizeof(double)));
+    h->handoff_cols = 6;    // measured on the config-3 batch: 4.7 M QP/s without, 5.0 M at 2-4, 6.2 M at 6-10, 5.5 M at 12 (tools/)
+    if (const char* ho = getenv("RQP_TUNE_HANDOFF")) h->handoff_cols = atoi(ho);   // (tuning aid of tools/mfma16_check.py, not a dispatch input)
+    return RQP_OK;
+}
+
+// rqp_setup behind its argument checks, on an empty handle.  A failure may leave a partial workspace behind: the caller frees it.
+int setup_workspace(rqp_handle* h, const void* H, const void* g, const void* A, const void* l, const void* u, hipStream_t s) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    int rc = select_kernels(h);
+    if (rc != RQP_OK) return rc;
+    // the streaming kernel backs every handle (iterate / residuals modes, sizes beyond the tiles): its vectors must fit LDS
+    if (const size_t lds = rqp_generic_lds_bytes(h); lds > 160 * 1024) {
+        char buf[256];
+        snprintf(buf, sizeof(buf), "rqp_setup: n=%d, m=%d needs %zu B of LDS for the vector state of the streaming kernel "
+                 "(limit 163840 B per workgroup)", h->n, h->m, lds);
+        return fail_unsupported(h, buf);
+    }
+    HIP_TRY(h, rqp_prepare_generic(h));
+    rc = alloc_core(h, s);
+    if (rc == RQP_OK && h->windowed) rc = alloc_window(h, s);
+    if (rc == RQP_OK && h->polish_reserved) rc = alloc_polish(h, s);
+    if (rc == RQP_OK && (h->adj_reserved || h->sens_reserved)) rc = alloc_adjoint(h, s);
+    if (rc == RQP_OK) rc = alloc_handoff(h);
+    if (rc != RQP_OK) return rc;
+    SetupArgs a = make_setup_args(h, H, g, A, l, u);
+    HIP_TRY(h, rqp_launch_pack_vecs(h, a, s));
+    if (h->dims.shared_mats && h->B > 1) {
+        // K is built from ONE equality pattern c (rho x 1e3 on rows with u - l <= eq_tol, reluqpth.py:54); the kernels
+        // scale rho by every instance's own c.  A shared-matrix batch must therefore share the pattern.
+        int32_t bad = 0;
+        HIP_TRY(h, rqp_launch_check_shared_c(h, h->flag_d, s));
+        HIP_TRY(h, hipMemcpyAsync(&bad, h->flag_d, sizeof(bad), hipMemcpyDeviceToHost, s));
+        HIP_TRY(h, hipStreamSynchronize(s));
+        if (bad)
+            return fail_unsupported(h, "rqp_setup: shared (H, A) batch whose instances differ in which rows are equalities (u - l <= eq_tol); "
+                                       "K(rho) is built per matrix, so pass H and A with a batch dimension for such a batch");
+    }
+    const auto t_alloc = std::chrono::steady_clock::now();
+    if ((rc = build_matrices(h, a, s)) != RQP_OK) return rc;
+    if (h->st.scaling > 0) HIP_TRY(h, rqp_launch_scale_vecs(h, h->g, h->l, h->u, s));    // g <- c D g, l/u <- E l/u
+    h->is_setup = true;
+    h->cold_state = true;
+    if ((rc = rqp_clear_primal_dual(h, s)) != RQP_OK) return rc;    // zero state, rho_ind0 (reluqpth.py:148-153)
+    if (h->debug & 1) {                         // host-side split of a setup call (synchronous, debug only)
+        const auto t_enq = std::chrono::steady_clock::now();
+        (void)hipStreamSynchronize(s);
+        const auto t_end = std::chrono::steady_clock::now();
+        auto ms = [](auto a0, auto a1) { return std::chrono::duration<double, std::milli>(a1 - a0).count(); };
+        fprintf(stderr, "[rqp] setup host split: allocate %.2f ms, enqueue %.2f ms, device drain %.2f ms\n", ms(t_begin, t_alloc),
+                ms(t_alloc, t_enq), ms(t_enq, t_end));
     }
     return RQP_OK;
 }
@@ -398,184 +615,10 @@ int rqp_setup(rqp_handle* h, const void* H, const void* g, const void* A, const 
               void* stream) {
     if (!h) return RQP_ERR_ARG;
     if (!H || !g || !A || !l || !u) return fail_arg(h, "rqp_setup: null input pointer");
-    hipStream_t s = (hipStream_t)stream;
     HIP_TRY(h, hipSetDevice(h->device));
-    const auto t_begin = std::chrono::steady_clock::now();
     free_ws(h);
-    {
-        const int rc = select_kernels(h);
-        if (rc != RQP_OK) return rc;
-    }
-    {
-        // the streaming kernel backs every handle (iterate / residuals modes, sizes beyond the tiles): its vectors must fit LDS
-        const size_t lds = rqp_generic_lds_bytes(h);
-        if (lds > 160 * 1024) {
-            char buf[256];
-            snprintf(buf, sizeof(buf), "rqp_setup: n=%d, m=%d needs %zu B of LDS for the vector state of the streaming kernel "
-                     "(limit 163840 B per workgroup)", h->n, h->m, lds);
-            h->err = buf;
-            return RQP_ERR_UNSUPPORTED;
-        }
-        HIP_TRY(h, rqp_prepare_generic(h));
-    }
-    const size_t n = h->n, m = h->m, B = h->B, nm = h->nmat, e = h->esz;
-    HIP_TRY(h, hipMalloc(&h->Ht, nm * n * h->ldn * e));
-    if (!h->borrow_A) HIP_TRY(h, hipMalloc(&h->A, nm * m * h->ldn * e));     // (rqp_common.h: borrow_A)
-    // A' (the streaming kernel's A dx operand and the wavefront kernel's column role): not on a windowed resident handle, whose
-    // solve / iterate / residuals all run on k_admm_res2 / k_admm_res64 (neither reads A') and which refuses the certificate pass
-    // (float32: 0.5 GB and 0.4 ms at B = 4096; float64: 1 GB and 1 ms)
-    if (!(h->windowed && (h->resident || h->resident64))) HIP_TRY(h, hipMalloc(&h->At, nm * n * h->ldm * e));
-    if (!h->kpack_direct) {   // (+ a zeroed tail: the low-memory K load of the resident kernel reads up to one vector past a row's end)
-        const size_t kb = nm * h->kwin * n * h->ldn * e;
-        HIP_TRY(h, hipMalloc(&h->K, kb + 256));
-        HIP_TRY(h, hipMemsetAsync((char*)h->K + kb, 0, 256, s));
-    }
-    HIP_TRY(h, hipMalloc(&h->g, B * n * e));
-    HIP_TRY(h, hipMalloc(&h->l, B * m * e));
-    HIP_TRY(h, hipMalloc(&h->u, B * m * e));
-    HIP_TRY(h, hipMalloc(&h->c, B * m * e));
-    HIP_TRY(h, hipMalloc((void**)&h->G, nm * n * n * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void**)&h->x, B * n * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void**)&h->z, B * m * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void**)&h->lam, B * m * sizeof(double)));
-    HIP_TRY(h, hipMalloc((void**)&h->rho_ind, B * sizeof(int32_t)));
-    HIP_TRY(h, hipMalloc((void**)&h->rhos_d, h->nrho * sizeof(double)));
-    HIP_TRY(h, hipMemcpyAsync(h->rhos_d, h->rhos.data(), h->nrho * sizeof(double), hipMemcpyHostToDevice, s));
-    const size_t lds_need = (n * n + 2 * n) * sizeof(double);
-    if (lds_need > 160 * 1024 - 512) {   // factor scratch in global memory
-        h->fscratch_elems = nm * h->kwin * n * n;
-        HIP_TRY(h, hipMalloc((void**)&h->fscratch, h->fscratch_elems * sizeof(double)));
-    }
-    HIP_TRY(h, hipMalloc((void**)&h->flag_d, sizeof(int32_t)));
-    if ((h->mfmal || h->mfmad) && h->B > 16)       // slot order of the streamed-operand MFMA kernels (grouped by starting rho index)
-        HIP_TRY(h, hipMalloc((void**)&h->order_d, (size_t)h->B * sizeof(int32_t)));
-    if (h->mfmal && h->B > 16) {                   // regrouped cold solve (rqp_mfmal.hip): exact state of the instances between its two launches
-        HIP_TRY(h, hipMalloc((void**)&h->ax_d, B * m * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->cont_rho_d, B * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->key_d, B * sizeof(int32_t)));
-    }
-    if (!h->use_mfma && h->B >= (h->resident64 ? 2 : 4) * h->ncu) {      // dispatch order (see rqp_common.h): batches that outlast one wave of workgroups
-        HIP_TRY(h, hipMalloc((void**)&h->order_d, (size_t)h->B * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void**)&h->last_iter_d, (size_t)h->B * sizeof(int32_t)));
-    }
-    if (h->windowed) {
-        const int w0 = std::min(std::max(h->rho_ind0 - 1, 0), h->nrho - h->kwin);
-        HIP_TRY(h, hipMalloc((void**)&h->wbase_d, nm * sizeof(int32_t)));
-        HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)h->wbase_d, w0, nm, s));
-        HIP_TRY(h, hipMalloc((void**)&h->ax_d, B * m * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->cstat_d, B * sizeof(int32_t)));
-        HIP_TRY(h, hipMemsetAsync(h->cstat_d, 0, B * sizeof(int32_t), s));
-        HIP_TRY(h, hipMalloc((void**)&h->ncont_d, 2 * sizeof(int32_t)));
-        HIP_TRY(h, hipHostMalloc((void**)&h->ncont_h, sizeof(int32_t), hipHostMallocDefault));
-        HIP_TRY(h, hipMalloc((void**)&h->cont_iter_d, B * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void**)&h->cont_rho_d, B * sizeof(double)));
-    }
-    if (h->polish_reserved) {   // solution polishing (rqp_polish.hip): chunked float64 workspace, per-instance results
-        const size_t lds = rqp_polish_lds_bytes(h);
-        if (lds > 160 * 1024) {
-            free_ws(h);
-            return fail_unsupported(h, "rqp_setup: polish needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
-        }
-        h->polish_chunk = rqp_polish_chunk(h);
-        const size_t pc = h->polish_chunk;
-        HIP_TRY(h, hipMalloc((void**)&h->polish_G, pc * n * n * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_Minv, pc * n * h->ldn * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_rho, sizeof(double)));
-        const double idel = 1.0 / h->polish_delta;
-        HIP_TRY(h, hipMemcpyAsync(h->polish_rho, &idel, sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_status, B * sizeof(int32_t)));
-        HIP_TRY(h, hipMemsetAsync(h->polish_status, 0, B * sizeof(int32_t), s));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_act, B * m));
-        HIP_TRY(h, hipMemsetAsync(h->polish_act, 0, B * m, s));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_flag, B * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_st_in, B * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void**)&h->polish_res_in, 3 * B * sizeof(double)));
-        HIP_TRY(h, hipStreamSynchronize(s));          // (idel lives on this stack frame)
-    }
-    if (h->adj_reserved && rqp_adjoint_lds_bytes(h) > 160 * 1024) {
-        free_ws(h);
-        return fail_unsupported(h, "rqp_setup: the adjoint needs 8 (4 n + 4 m + 264) bytes of LDS, above 160 KB");
-    }
-    if (h->sens_reserved && rqp_sens_lds_bytes(h) > 160 * 1024) {
-        free_ws(h);
-        return fail_unsupported(h, "rqp_setup: the sensitivities need 384 ceil16(n) + 2 KB of LDS, above 160 KB");
-    }
-    if (h->adj_reserved || h->sens_reserved) {
-        // adjoint (rqp_adjoint.hip) and forward sensitivities (rqp_sens.hip): packed caller matrices, G_a and M^-1 per chunk
-        h->adj_chunk = rqp_polish_chunk(h);
-        const size_t pc = h->adj_chunk, pm = h->dims.shared_mats ? 1 : pc;
-        HIP_TRY(h, hipMalloc(&h->adj_Ht, pm * n * h->ldn * e));
-        HIP_TRY(h, hipMalloc(&h->adj_A, pm * m * h->ldn * e));
-        if (h->polish_reserved) {               // (same chunk rule: polish's buffers hold one chunk of either)
-            h->adj_G = h->polish_G;
-            h->adj_Minv = h->polish_Minv;
-        } else {
-            HIP_TRY(h, hipMalloc((void**)&h->adj_G_own, pc * n * n * sizeof(double)));
-            HIP_TRY(h, hipMalloc((void**)&h->adj_Minv_own, pc * n * h->ldn * sizeof(double)));
-            h->adj_G = h->adj_G_own;
-            h->adj_Minv = h->adj_Minv_own;
-        }
-        HIP_TRY(h, hipMalloc((void**)&h->adj_rho, sizeof(double)));
-        const double idel = 1.0 / h->adj_delta;
-        HIP_TRY(h, hipMemcpyAsync(h->adj_rho, &idel, sizeof(double), hipMemcpyHostToDevice, s));
-        HIP_TRY(h, hipMalloc((void**)&h->adj_flag, B * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void**)&h->adj_act, B * m));
-        if (h->adj_reserved)                    // per-instance rows of the matrix gradients
-            HIP_TRY(h, hipMalloc((void**)&h->adj_rows, B * (2 * n + 2 * m) * sizeof(double)));
-        if (h->sens_reserved) {                 // active-row lists, one chunk of direction blocks
-            HIP_TRY(h, hipMalloc((void**)&h->sens_idx, B * m * sizeof(int32_t)));
-            HIP_TRY(h, hipMalloc((void**)&h->sens_pos, B * m * sizeof(int32_t)));
-            HIP_TRY(h, hipMalloc((void**)&h->sens_na, B * sizeof(int32_t)));
-            HIP_TRY(h, hipMalloc((void**)&h->sens_ws, pc * rqp_sens_ws_doubles(h) * sizeof(double)));
-        }
-        HIP_TRY(h, hipStreamSynchronize(s));          // (idel lives on this stack frame)
-    }
-    h->handoff_cols = 0;
-    if (h->use_mfma && h->resident && (h->B + 15) / 16 <= h->ncu) {   // straggler hand-off (SolveArgs): one tile per CU at most
-        HIP_TRY(h, hipMalloc((void**)&h->cont_iter_d, (size_t)h->B * sizeof(int32_t)));
-        HIP_TRY(h, hipMalloc((void**)&h->cont_rho_d, (size_t)h->B * sizeof(double)));
-        h->handoff_cols = 6;    // measured on the config-3 batch: 4.7 M QP/s without, 5.0 M at 2-4, 6.2 M at 6-10, 5.5 M at 12 (tools/)
-        if (const char* ho = getenv("RQP_TUNE_HANDOFF")) h->handoff_cols = atoi(ho);   // (tuning aid of tools/mfma16_check.py, not a dispatch input)
-    }
-    SetupArgs a = make_setup_args(h, H, g, A, l, u);
-    HIP_TRY(h, rqp_launch_pack_vecs(h, a, s));
-    if (h->dims.shared_mats && h->B > 1) {
-        // K is built from ONE equality pattern c (rho x 1e3 on rows with u - l <= eq_tol, reluqpth.py:54); the kernels
-        // scale rho by every instance's own c.  A shared-matrix batch must therefore share the pattern.
-        int32_t bad = 0;
-        HIP_TRY(h, rqp_launch_check_shared_c(h, h->flag_d, s));
-        HIP_TRY(h, hipMemcpyAsync(&bad, h->flag_d, sizeof(bad), hipMemcpyDeviceToHost, s));
-        HIP_TRY(h, hipStreamSynchronize(s));
-        if (bad) {
-            free_ws(h);
-            h->err = "rqp_setup: shared (H, A) batch whose instances differ in which rows are equalities (u - l <= eq_tol); "
-                     "K(rho) is built per matrix, so pass H and A with a batch dimension for such a batch";
-            return RQP_ERR_UNSUPPORTED;
-        }
-    }
-    if (h->st.scaling > 0) {
-        HIP_TRY(h, hipMalloc((void**)&h->Dsc, nm * n * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->Esc, nm * m * sizeof(double)));
-        HIP_TRY(h, hipMalloc((void**)&h->csc, nm * sizeof(double)));
-    }
-    const auto t_alloc = std::chrono::steady_clock::now();
-    int rc = build_matrices(h, a, s);
-    if (rc != RQP_OK) {
-        free_ws(h);
-        return rc;
-    }
-    if (h->st.scaling > 0) HIP_TRY(h, rqp_launch_scale_vecs(h, h->g, h->l, h->u, s));    // g <- c D g, l/u <- E l/u
-    h->is_setup = true;
-    h->cold_state = true;
-    rc = rqp_clear_primal_dual(h, stream);      // zero state, rho_ind0 (reluqpth.py:148-153)
-    if (h->debug & 1) {                         // host-side split of a setup call (synchronous, debug only)
-        const auto t_enq = std::chrono::steady_clock::now();
-        (void)hipStreamSynchronize(s);
-        const auto t_end = std::chrono::steady_clock::now();
-        auto ms = [](auto a0, auto a1) { return std::chrono::duration<double, std::milli>(a1 - a0).count(); };
-        fprintf(stderr, "[rqp] setup host split: allocate %.2f ms, enqueue %.2f ms, device drain %.2f ms\n", ms(t_begin, t_alloc),
-                ms(t_alloc, t_enq), ms(t_enq, t_end));
-    }
+    const int rc = setup_workspace(h, H, g, A, l, u, (hipStream_t)stream);
+    if (rc != RQP_OK) free_ws(h);               // every failure past this point leaves an empty handle; h->err says why
     return rc;
 }
 
@@ -685,7 +728,7 @@ static int refactor_windows(rqp_handle* h, int all, const int32_t* gate, hipStre
     f.gate = gate;
     set_kp_image(h, f);
     HIP_TRY(h, rqp_launch_factor(h, f, s));
-    if (h->resident) HIP_TRY(h, rqp_launch_pack_res2(h, nullptr, h->cstat_d, gate, s));
+    if (uses_res2(h)) HIP_TRY(h, rqp_launch_pack_res2(h, nullptr, h->cstat_d, gate, s));
     return RQP_OK;
 }
 
@@ -715,7 +758,7 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
     }
     // Infeasibility certificates: the streaming kernel tests them at every check; the register-resident / MFMA kernels
     // keep their loops untouched and a mode-3 pass of the streaming kernel examines the instances that ran out of iterations.
-    const bool post_cert = h->st.check_infeasibility && a.info.status && (h->use_mfma || h->use_wave || h->resident || h->resident64);
+    const bool post_cert = h->st.check_infeasibility && a.info.status && h->solve_kernel != RQP_K_GENERIC;
     if (post_cert) a.keep_state = 1;
     // Solution polishing reads the final iterate of every instance: with warm_starting = 0 the state is kept through the chain
     // and cleared after the polish kernels (what the solve kernels would have done at their exit).  (On k_admm_mfmal this turns
@@ -723,7 +766,7 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
     const bool polish = h->polish_reserved && h->polish_on;
     const bool polish_keep = polish && !h->st.warm_starting;
     if (polish_keep) a.keep_state = 1;
-    const bool handoff = h->use_mfma && h->handoff_cols > 0 && a.info.status != nullptr;
+    const bool handoff = h->handoff_cols > 0 && a.info.status != nullptr;      // (alloc_handoff: tile kernels backed by k_admm_res2)
     if (handoff) {
         a.handoff_cols = h->handoff_cols;
         a.cont_iter = h->cont_iter_d;
@@ -744,7 +787,7 @@ int rqp_solve(rqp_handle* h, void* x, void* z, void* lam, const rqp_info* info, 
         c.keep_state = (post_cert || polish_keep) ? 1 : 0;
         c.order = nullptr;
         c.last_iter = nullptr;
-        HIP_TRY(h, rqp_launch_solve_res2(h, c, s));
+        HIP_TRY(h, rqp_kernels[h->aux_kernel].solve(h, c, s));
     }
     const bool ranks = h->order_d && h->last_iter_d && h->use_history;   // rank the instances by what they just needed: next launch goes longest-first
     if (fixed_passes) {
@@ -1030,7 +1073,7 @@ int rqp_get_dispatch(rqp_handle* h, int32_t* order, int32_t* last_iter, int32_t*
     return RQP_OK;
 }
 
-const char* rqp_kernel_name(const rqp_handle* h) { return h ? h->kernel_name : ""; }
+const char* rqp_kernel_name(const rqp_handle* h) { return h ? rqp_kernels[h->solve_kernel].name : ""; }
 
 const char* rqp_strerror(int err) {
     switch (err) {

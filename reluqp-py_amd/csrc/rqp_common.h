@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -14,6 +15,20 @@
 #define RQP_WINDOW 5        // K(rho) slots per matrix of a windowed handle (rho_ind0 - 1 .. rho_ind0 + 3 at setup)
 #define RQP_NT 256          // threads per workgroup of the generic kernels (4 wavefronts)
 #define RQP_WAVE 64         // CDNA wavefront
+
+// The ADMM kernels.  A handle names two of them (select_kernels, rqp_abi.hip); what each one is -- its name, its launcher, the
+// operand-image functions of the 16-instance-tile kernels -- stands in ONE table, rqp_kernels[] (rqp_abi.hip).
+enum rqp_kernel_id {
+    RQP_K_GENERIC,   // rqp_admm.hip: the streaming kernel, any size that fits LDS, every mode
+    RQP_K_RES2,      // rqp_resident2.hip: float32, A and K in VGPRs (n <= 104, m <= 320); solve, iterate, residuals, continuations
+    RQP_K_RES64,     // rqp_res64.hip: the float64 resident kernel (n <= 104, m <= 320); the same modes
+    RQP_K_WAVE,      // rqp_wave.hip: one wavefront per instance (n <= 32, m <= 64); solve only
+    RQP_K_MFMA,      // rqp_mfma.hip: shared-(H,A) batches in 16-instance tiles, operands in registers; solve only, as every tile kernel
+    RQP_K_MFMA16,    // rqp_mfma16.hip: ... on the bf16 matrix pipe (tile_dtype = RQP_TILE_BF16)
+    RQP_K_MFMAL,     // rqp_mfmal.hip: ... large / sparse problems, operands streamed from L2 (n <= 320, m <= 640)
+    RQP_K_MFMAD,     // rqp_mfmad.hip: ... the same in float64 on v_mfma_f64_16x16x4_f64 (n <= 160, m <= 320)
+    RQP_K_COUNT
+};
 
 // ---------------------------------------------------------------------------------------
 // Workspace layout (all device memory, owned by the handle).  T = float | double.
@@ -52,13 +67,9 @@ struct rqp_handle {
     float *Apack = nullptr, *Kpack = nullptr, *Hpack = nullptr;
     bool k_direct = false;        // RQP_FLAG_LOW_MEMORY on the float32 resident kernel: no Kpack, K read from the row-major table
     float* Kscale = nullptr;      // [nmat][nrho] power-of-two scale of the fp16 K tile (tile_dtype = RQP_TILE_F16)
-    bool resident = false;        // rqp_resident2.hip: A, K in VGPRs (solve, iterate and residuals modes)
-    bool resident64 = false;      // rqp_res64.hip: the float64 resident kernel (n <= 104, m <= 320), all modes
-    bool use_wave = false;        // rqp_wave.hip: one wavefront per instance (n <= 32, m <= 64), solve() only
-    bool use_mfma = false;        // rqp_mfma.hip: shared-(H,A) batches, solve() only
-    bool mfma16 = false;          // ... on the bf16 matrix pipe (rqp_mfma16.hip, tile_dtype = RQP_TILE_BF16)
-    bool mfmal = false;           // ... large / sparse problems, operands streamed from L2 (rqp_mfmal.hip: n <= 320, m <= 640)
-    bool mfmad = false;           // ... the same in float64 on v_mfma_f64_16x16x4_f64 (rqp_mfmad.hip: n <= 160, m <= 320)
+    rqp_kernel_id solve_kernel = RQP_K_GENERIC;   // runs rqp_solve (mode 0), the window continuation passes (cont = 2) included
+    rqp_kernel_id aux_kernel = RQP_K_GENERIC;     // runs iterate / residuals (modes 1, 2) and the hand-off continuation (cont = 1):
+                                                  // the solve kernel itself, or RQP_K_RES2 / RQP_K_GENERIC behind a solve-only one
     float* W1img = nullptr;       // lane-linear MFMA operand images ([A; H'], A, K_j)
     int* queue = nullptr;         // next-instance counter of the persistent MFMA grid
     int32_t* flag_d = nullptr;    // device scratch flag (setup-time validation)
@@ -127,10 +138,8 @@ struct rqp_handle {
     int adj_refine = 3;
     int adj_chunk = 0;
     void *adj_Ht = nullptr, *adj_A = nullptr;
-    double* adj_G = nullptr;            // [adj_chunk][n][n]  (== polish_G when polish is reserved: not owned)
-    double* adj_Minv = nullptr;         // [adj_chunk][n][ldn] (== polish_Minv when polish is reserved: not owned)
-    double* adj_G_own = nullptr;        // the buffers above when the adjoint owns them
-    double* adj_Minv_own = nullptr;
+    double* adj_G = nullptr;            // [adj_chunk][n][n]   an allocation of its own, or polish_G when polish is reserved
+    double* adj_Minv = nullptr;         // [adj_chunk][n][ldn] ... or polish_Minv (an alias is not in `owned`: polish's entry frees it)
     double* adj_rho = nullptr;          // [1] 1 / delta
     int32_t* adj_flag = nullptr;        // [B] 1: differentiate this instance (its status is RQP_STATUS_SOLVED)
     int8_t* adj_act = nullptr;          // [B][m] the active set used
@@ -145,7 +154,9 @@ struct rqp_handle {
     int32_t* sens_na = nullptr;         // [B]
     double* sens_ws = nullptr;          // [adj_chunk][n + 4 m][16]: r1, r2, dy_a, A_a dx, dA x
 
-    const char* kernel_name = "generic";
+    // Every device allocation of the workspace, as the address of the field that holds it (the handle lives on the heap and never
+    // moves).  dev_alloc (rqp_abi.hip) is the only writer; free_ws frees and clears every entry.
+    std::vector<void**> owned;
     std::string err;
 };
 
@@ -304,6 +315,20 @@ size_t rqp_mfma16_img_elems(const rqp_handle* h);
 hipError_t rqp_launch_pack_mfma16(const rqp_handle* h, hipStream_t s);
 hipError_t rqp_prepare_mfma16(const rqp_handle* h);
 hipError_t rqp_launch_solve_mfma16(const rqp_handle* h, const SolveArgs& a, hipStream_t s);
+
+// What an ADMM kernel is to the host layer: rqp_kernels[id] in rqp_abi.hip.  name: rqp_kernel_name.  The last three belong to the
+// 16-instance-tile kernels (NULL otherwise): 4-byte words of the operand image W1img, launch preparation, image build.
+struct rqp_kernel_desc {
+    const char* name;
+    hipError_t (*solve)(const rqp_handle* h, const SolveArgs& a, hipStream_t s);
+    size_t (*img_elems)(const rqp_handle* h);
+    hipError_t (*prepare)(const rqp_handle* h);
+    hipError_t (*pack)(const rqp_handle* h, hipStream_t s);
+};
+
+// RQP_DIAG builds of the ADMM kernels stamp a tick buffer [groups][waves][slots] of 64-bit counters.  Allocates it, calls
+// `launch(ticks)`, drains the stream and returns tot[w * slots + e] = the sum over the workgroups; empty when the allocation failed.
+std::vector<double> rqp_diag_run(hipStream_t s, size_t groups, int waves, int slots, const std::function<void(unsigned long long*)>& launch);
 
 // Raise -- never lower -- the dynamic-LDS limit of kernel `fn` on the current device.  The attribute belongs to the FUNCTION, not
 // to a handle: a later, smaller handle must not shrink the limit an earlier, larger handle's launches rely on (process-wide

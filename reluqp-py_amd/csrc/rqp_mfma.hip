@@ -934,32 +934,25 @@ hipError_t rqp_launch_solve_mfma(const rqp_handle* h, const SolveArgs& a0, hipSt
         e = hipMemsetAsync(queue, 0, sizeof(int), s);
         if (e != hipSuccess) return e;
     }
-    {
-        if (h->debug & 2) {      // diagnostic build: per-segment cycle shares of the iteration (synchronous, debug only)
-            unsigned long long* dbg = nullptr;
-            const size_t cnt = (size_t)grid * 4 * 12;
-            if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
+    if (h->debug & 2) {          // diagnostic build: per-segment cycle shares of the iteration (synchronous, debug only)
+        const std::vector<double> sums = rqp_diag_run(s, grid, 4, 12, [&](unsigned long long* dbg) {
             k_admm_mfma<CfgM55, true><<<grid, CfgM55::NT, lds, s>>>(a, h->W1img, queue, dbg);
-            (void)hipStreamSynchronize(s);
-            std::vector<unsigned long long> hb(cnt);
-            (void)hipMemcpy(hb.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-            (void)hipFree(dbg);
-            static const char* names[11] = {"top wait", "GEMM1", "wait", "d", "wait", "GEMM2", "wait", "x", "wait", "GEMM3+rows", "next"};
-            for (int w = 0; w < 4; ++w) {
-                double tot[12] = {0};
-                for (int t = 0; t < grid; ++t)
-                    for (int e2 = 0; e2 < 12; ++e2) tot[e2] += (double)hb[((size_t)t * 4 + w) * 12 + e2];
-                fprintf(stderr, "[rqp diag mfma] wave %d, %.1f iterations/workgroup, s_memtime ticks per iteration:", w, tot[11] / grid);
-                for (int e2 = 0; e2 < 11; ++e2)
-                    if (e2 != 3 && e2 != 4) fprintf(stderr, "  %s %.1f", names[e2], tot[e2] / tot[11]);
-                double it = 0;
-                for (int e2 = 0; e2 < 11; ++e2)
-                    if (e2 != 3 && e2 != 4) it += tot[e2];
-                fprintf(stderr, "\n[rqp diag mfma] wave %d per workgroup: total %.0f ticks = prologue %.0f + iterations %.0f + load/start/check/exit %.0f\n", w,
-                        tot[4] / grid, tot[3] / grid, it / grid, (tot[4] - tot[3] - it) / grid);
+        });
+        if (sums.empty()) return hipErrorOutOfMemory;
+        static const char* names[11] = {"top wait", "GEMM1", "wait", "d", "wait", "GEMM2", "wait", "x", "wait", "GEMM3+rows", "next"};
+        for (int w = 0; w < 4; ++w) {
+            const double* tot = &sums[(size_t)w * 12];
+            fprintf(stderr, "[rqp diag mfma] wave %d, %.1f iterations/workgroup, s_memtime ticks per iteration:", w, tot[11] / grid);
+            double it = 0;
+            for (int e2 = 0; e2 < 11; ++e2) {
+                if (e2 == 3 || e2 == 4) continue;        // (prologue and total: the second line)
+                fprintf(stderr, "  %s %.1f", names[e2], tot[e2] / tot[11]);
+                it += tot[e2];
             }
-            return hipGetLastError();
+            fprintf(stderr, "\n[rqp diag mfma] wave %d per workgroup: total %.0f ticks = prologue %.0f + iterations %.0f + load/start/check/exit %.0f\n", w,
+                    tot[4] / grid, tot[3] / grid, it / grid, (tot[4] - tot[3] - it) / grid);
         }
+        return hipGetLastError();
     }
     k_admm_mfma<CfgM55, false><<<grid, CfgM55::NT, lds, s>>>(a, h->W1img, queue, nullptr);
     return hipGetLastError();

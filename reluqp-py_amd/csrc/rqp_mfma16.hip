@@ -977,19 +977,13 @@ hipError_t rqp_launch_solve_mfma16(const rqp_handle* h, const SolveArgs& a0, hip
         if (e != hipSuccess) return e;
     }
     if (h->debug & 2) {          // diagnostic build: per-segment cycle shares of the iteration (synchronous, debug only)
-        unsigned long long* dbg = nullptr;
-        const size_t cnt = (size_t)grid * 4 * 12;
-        if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
-        k_admm_mfma16<Cfg16M55, true><<<grid, Cfg16M55::NT, lds, s>>>(a, (const unsigned*)h->W1img, queue, dbg);
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> hb(cnt);
-        (void)hipMemcpy(hb.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
+        const std::vector<double> sums = rqp_diag_run(s, grid, 4, 12, [&](unsigned long long* dbg) {
+            k_admm_mfma16<Cfg16M55, true><<<grid, Cfg16M55::NT, lds, s>>>(a, (const unsigned*)h->W1img, queue, dbg);
+        });
+        if (sums.empty()) return hipErrorOutOfMemory;
         static const char* names[11] = {"top wait", "GEMM1", "wait", "d", "wait", "GEMM2", "wait", "x", "wait", "GEMM3+rows", "next"};
         for (int w = 0; w < 4; ++w) {
-            double tot[12] = {0};
-            for (int t = 0; t < grid; ++t)
-                for (int e2 = 0; e2 < 12; ++e2) tot[e2] += (double)hb[((size_t)t * 4 + w) * 12 + e2];
+            const double* tot = &sums[(size_t)w * 12];
             fprintf(stderr, "[rqp diag mfma16] wave %d, %.1f iterations/workgroup, cycles per iteration:", w, tot[11] / grid);
             double it = 0;
             for (int e2 = 0; e2 < 11; ++e2) { fprintf(stderr, "  %s %.0f", names[e2], tot[e2] / tot[11]); it += tot[e2] / tot[11]; }

@@ -798,19 +798,11 @@ hipError_t rqp_launch_solve_mfmad(const rqp_handle* h, const SolveArgs& a0, hipS
     }
     const int* img = (const int*)h->W1img;
     if (h->debug & 2) {          // diagnostic build: per-segment tick shares of the iteration (synchronous, debug only)
-        unsigned long long* dbg = nullptr;
-        const size_t cnt = (size_t)grid * MD_NW * 12;
-        if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
-        k_admm_mfmad<true><<<grid, MD_NT, md_lds_bytes(), s>>>(a, img, dbg);
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> hb(cnt);
-        (void)hipMemcpy(hb.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
+        const std::vector<double> sums = rqp_diag_run(s, grid, MD_NW, 12, [&](unsigned long long* dbg) { k_admm_mfmad<true><<<grid, MD_NT, md_lds_bytes(), s>>>(a, img, dbg); });
+        if (sums.empty()) return hipErrorOutOfMemory;
         static const char* names[10] = {"top wait", "GEMM1", "d", "wait", "GEMM2", "x", "wait", "GEMM3", "rows", "next"};
         for (int w = 0; w < MD_NW; ++w) {
-            double tot[12] = {0};
-            for (int t = 0; t < grid; ++t)
-                for (int e2 = 0; e2 < 12; ++e2) tot[e2] += (double)hb[((size_t)t * MD_NW + w) * 12 + e2];
+            const double* tot = &sums[(size_t)w * 12];
             fprintf(stderr, "[rqp diag mfmad] wave %d, %.1f iterations/workgroup, s_memtime ticks per iteration:", w, tot[11] / grid);
             double it = 0;
             for (int e2 = 0; e2 < 10; ++e2) {

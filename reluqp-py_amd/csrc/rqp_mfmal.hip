@@ -863,24 +863,18 @@ hipError_t rqp_launch_solve_mfmal(const rqp_handle* h, const SolveArgs& a0, hipS
         return hipGetLastError();
     }
     if (h->debug & 2) {          // diagnostic build: per-segment tick shares of the iteration (synchronous, debug only)
-        unsigned long long* dbg = nullptr;
-        const size_t cnt = (size_t)grid * ML_NW * 12;
-        if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
         const char* ex = getenv("RQP_MLEXP");
         const int exv = ex ? atoi(ex) : 0;
-        if (exv == 1) k_admm_mfmal<true, 1><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
-        else if (exv == 2) k_admm_mfmal<true, 2><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
-        else if (exv == 3) k_admm_mfmal<true, 3><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
-        else k_admm_mfmal<true><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> hb(cnt);
-        (void)hipMemcpy(hb.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
+        const std::vector<double> sums = rqp_diag_run(s, grid, ML_NW, 12, [&](unsigned long long* dbg) {
+            if (exv == 1) k_admm_mfmal<true, 1><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
+            else if (exv == 2) k_admm_mfmal<true, 2><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
+            else if (exv == 3) k_admm_mfmal<true, 3><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
+            else k_admm_mfmal<true><<<grid, ML_NT, ml_lds_floats() * sizeof(float), s>>>(a, h->W1img, dbg);
+        });
+        if (sums.empty()) return hipErrorOutOfMemory;
         static const char* names[10] = {"top wait", "GEMM1", "d", "wait", "GEMM2", "x", "wait", "GEMM3", "rows", "next"};
         for (int w = 0; w < ML_NW; ++w) {
-            double tot[12] = {0};
-            for (int t = 0; t < grid; ++t)
-                for (int e2 = 0; e2 < 12; ++e2) tot[e2] += (double)hb[((size_t)t * ML_NW + w) * 12 + e2];
+            const double* tot = &sums[(size_t)w * 12];
             fprintf(stderr, "[rqp diag mfmal] wave %d, %.1f iterations/workgroup, s_memtime ticks per iteration:", w, tot[11] / grid);
             double it = 0;
             for (int e2 = 0; e2 < 10; ++e2) {

@@ -547,21 +547,12 @@ hipError_t rqp_prepare_res64(const rqp_handle* h) {
 hipError_t rqp_launch_solve_res64(const rqp_handle* h, const SolveArgs& a, hipStream_t s) {
     const size_t lds = r64_lds_doubles() * sizeof(double);
     if (h->debug & 2) {          // diagnostic build: per-segment cycle shares of the iteration (synchronous, debug only)
-        unsigned long long* dbg = nullptr;
-        const size_t cnt = (size_t)h->B * R64_NW * 9;
-        if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
-        k_admm_res64<true><<<h->B, R64_NT, lds, s>>>(a, dbg);
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> hbuf(cnt);
-        (void)hipMemcpy(hbuf.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
+        const std::vector<double> sums = rqp_diag_run(s, h->B, R64_NW, 9, [&](unsigned long long* dbg) { k_admm_res64<true><<<h->B, R64_NT, lds, s>>>(a, dbg); });
+        if (sums.empty()) return hipErrorOutOfMemory;
         static const char* names[8] = {"B3 wait", "A'nu+Hx", "B1 wait", "Kd+x", "A dx", "B2 wait", "rows", "check"};
         for (int w = 0; w < R64_NW; ++w) {
-            double tot[8] = {0}, its = 0;
-            for (int b = 0; b < h->B; ++b) {
-                for (int e = 0; e < 8; ++e) tot[e] += (double)hbuf[((size_t)b * R64_NW + w) * 9 + e];
-                its += (double)hbuf[((size_t)b * R64_NW + w) * 9 + 8];
-            }
+            const double* tot = &sums[(size_t)w * 9];
+            const double its = tot[8];
             fprintf(stderr, "[rqp diag64] wave %d cycles/iteration:", w);
             double sum = 0;
             for (int e = 0; e < 8; ++e) { fprintf(stderr, " %s=%.0f", names[e], tot[e] / its); sum += tot[e] / its; }

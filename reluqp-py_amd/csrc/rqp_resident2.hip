@@ -1201,21 +1201,15 @@ static hipError_t solve_t(const rqp_handle* h, const SolveArgs& a, hipStream_t s
         return hipGetLastError();
     }
     if ((h->debug & 2) && !h->k_direct) {   // diagnostic build: per-segment cycle shares of the iteration (synchronous, debug only)
-        unsigned long long* dbg = nullptr;
-        const size_t cnt = (size_t)h->B * 4 * NSEG;
-        if (hipMalloc((void**)&dbg, cnt * 8) != hipSuccess) return hipErrorOutOfMemory;
-        k_admm_res2<C, true, false><<<h->B, C::NT, lds, s>>>(a, h->Apack, h->Kpack, h->Hpack, dbg, nullptr);
-        (void)hipStreamSynchronize(s);
-        std::vector<unsigned long long> hbuf(cnt);
-        (void)hipMemcpy(hbuf.data(), dbg, cnt * 8, hipMemcpyDeviceToHost);
-        (void)hipFree(dbg);
+        const std::vector<double> sums = rqp_diag_run(s, h->B, 4, NSEG, [&](unsigned long long* dbg) {
+            k_admm_res2<C, true, false><<<h->B, C::NT, lds, s>>>(a, h->Apack, h->Kpack, h->Hpack, dbg, nullptr);
+        });
+        if (sums.empty()) return hipErrorOutOfMemory;
         static const char* names[22] = {"B3 wait", "A'nu+Hx", "B1 wait", "Kd+x", "A dx", "B2 wait", "-", "rows",
                                         "rows(a)", "res rows", "R1 wait", "A'lam", "Hx", "R2 wait", "norms+reduce", "R3 wait", "combine",
                                         "R4 wait", "decision", "K issue+rho rows", "K wait", "rows(b)"};
         for (int w = 0; w < 4; ++w) {
-            double tot[NSEG] = {0};
-            for (int b = 0; b < h->B; ++b)
-                for (int e = 0; e < NSEG; ++e) tot[e] += (double)hbuf[((size_t)b * 4 + w) * NSEG + e];
+            const double* tot = &sums[(size_t)w * NSEG];
             const double its = tot[NSEG - 1], chk = tot[22] > 0 ? tot[22] : 1.0;
             // the segments of an ordinary iteration, with the whole check as one figure ("check"), per iteration ...
             fprintf(stderr, "[rqp diag] wave %d cycles/iteration:", w);
