@@ -475,6 +475,39 @@ int rqp_ltv_adjoint_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes);
  * adjoint_workspace NULL, or a flag names an input whose pointer is NULL.                                                  */
 int rqp_ltv_condense_adjoint(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io, void* stream);
 
+/* ---- Stage constraints of LTV MPC problems (DESIGN.md section 5 "LTV condensing, stage constraints") ----
+ * Instead of the box on y, every stage k of every instance carries nc rows  lo_k <= E_k [u_k ; x_{k+1}] <= hi_k
+ * (E_k [nc][nu + nx]; u_k is the plant's input -K x_k + v_k), m_c = horizon nc rows in all.  With y = F v + s, s = G x0 + f as
+ * rqp_ltv_condense left them in the workspace (only read here):
+ *     A_c = E F  (block row k = E_k times the rows k (nu + nx) .. of F),   l_c = lo - E s,   u_c = hi - E s;
+ * H and g are those of rqp_ltv_condense / rqp_ltv_vectors.  Block row k of A_c is summed over the columns < (k + 1) nu, where F
+ * can be non-zero, and is exactly zero to the right whatever E holds; an infinite lo / hi entry comes back infinite.
+ * E is [batch][horizon][nc][nu + nx], or [horizon][nc][nu + nx] with RQP_LTV_STAGE_SHARED_E; lo, hi are [m_c], or [batch][m_c]
+ * with RQP_LTV_BOUNDS_BATCHED; outputs A_c [batch][m_c][n], l_c, u_c [batch][m_c].  Everything batched is a DEVICE array of
+ * dims.dtype.  The contract of the other rqp_ltv_* calls holds: float64 arithmetic, every output rounded once, enqueued on
+ * `stream` of `device`, no allocation, no host synchronisation, no atomics, a launch chain that depends on dims, nc and on which
+ * pointers are NULL only (capturable in a HIP graph), the caller's current device restored, rqp_last_error(NULL).
+ * Sizes: those of rqp_ltv_condense and 1 <= nc <= 32, m_c <= 640, else RQP_ERR_UNSUPPORTED.  RQP_ERR_ARG: a NULL pointer
+ * that is not marked optional.  RQP_LTV_STAGE_SHARED_E is a flag of these three calls only.                                  */
+#define RQP_LTV_STAGE_SHARED_E 32  /* E is [horizon][nc][nu+nx] (else [batch][...])                        */
+int rqp_ltv_stage_rows(const rqp_ltv_dims* dims, int device, int32_t nc, const void* E, const void* workspace, void* A_c,
+                       void* stream);
+int rqp_ltv_stage_vectors(const rqp_ltv_dims* dims, int device, int32_t nc, const void* E, const void* x0, const void* lo,
+                          const void* hi, const void* workspace, void* l_c, void* u_c, void* stream);
+
+/* Reverse mode of the two calls above, t = dl_c + du_c:
+ *     dA_full = E' dA_c (block row k = E_k' dA_c,k; exact zeros right of the staircase),   dl_full = E' t,
+ *     dE_k = dA_c,k F_k' - t_k s_k'   (per instance also when E is shared: the batch sum is the caller's).
+ * dA_full and dl_full are the dA and dl of rqp_ltv_condense_adjoint (du = NULL there: l = l_add - s there, l_c = lo - E s here);
+ * the gradients of lo, hi are dl_c, du_c themselves.  Whatever finite values dA_c holds right of the staircase are not read.  */
+typedef struct rqp_ltv_stage_adjoint_io {
+    const void *E, *x0;          /* as in the forward calls                                                              */
+    const void* workspace;       /* the forward workspace as rqp_ltv_condense left it for this linearisation (read only) */
+    const void *dA_c, *dl_c, *du_c; /* cotangents [batch][m_c][n], [batch][m_c] x 2; NULL = 0                            */
+    void *dA_full, *dl_full, *dE;/* outputs [batch][m][n], [batch][m], [batch][horizon][nc][nu+nx]; NULL = not wanted    */
+} rqp_ltv_stage_adjoint_io;
+int rqp_ltv_stage_adjoint(const rqp_ltv_dims* dims, int device, int32_t nc, const rqp_ltv_stage_adjoint_io* io, void* stream);
+
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);
 

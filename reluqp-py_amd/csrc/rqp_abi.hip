@@ -1183,6 +1183,54 @@ int rqp_ltv_condense_adjoint(const rqp_ltv_dims* dims, int device, const rqp_ltv
     return RQP_OK;
 }
 
+// Stage constraints: dims as in the calls above plus RQP_LTV_STAGE_SHARED_E, a flag of these three entry points alone (the
+// shared checks see the dims without it, so they keep refusing it everywhere else).
+static int ltv_stage_check(const rqp_ltv_dims* dims, int32_t nc, const char* fn) {
+    if (!dims) return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": dims is NULL");
+    rqp_ltv_dims d = *dims;
+    d.flags &= ~RQP_LTV_STAGE_SHARED_E;
+    if (int rc = ltv_check(&d, fn)) return rc;
+    if (const char* w = rqp_ltv_stage_check_size(dims, nc)) return ltv_fail(RQP_ERR_UNSUPPORTED, std::string(fn) + ": " + w);
+    return RQP_OK;
+}
+
+int rqp_ltv_stage_rows(const rqp_ltv_dims* dims, int device, int32_t nc, const void* E, const void* workspace, void* A_c,
+                       void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_stage_check(dims, nc, "rqp_ltv_stage_rows")) return rc;
+    if (!E || !workspace || !A_c) return ltv_fail(RQP_ERR_ARG, "rqp_ltv_stage_rows: E, workspace and A_c are required");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_stage_rows")) return rc;
+    hipError_t e = rqp_ltv_launch_stage_rows(dims, nc, E, workspace, A_c, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_stage_rows: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+int rqp_ltv_stage_vectors(const rqp_ltv_dims* dims, int device, int32_t nc, const void* E, const void* x0, const void* lo,
+                          const void* hi, const void* workspace, void* l_c, void* u_c, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_stage_check(dims, nc, "rqp_ltv_stage_vectors")) return rc;
+    if (!E || !x0 || !lo || !hi || !workspace || !l_c || !u_c)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_stage_vectors: E, x0, lo, hi, workspace, l_c and u_c are required");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_stage_vectors")) return rc;
+    hipError_t e = rqp_ltv_launch_stage_vectors(dims, nc, E, x0, lo, hi, workspace, l_c, u_c, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_stage_vectors: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+int rqp_ltv_stage_adjoint(const rqp_ltv_dims* dims, int device, int32_t nc, const rqp_ltv_stage_adjoint_io* io, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_stage_check(dims, nc, "rqp_ltv_stage_adjoint")) return rc;
+    if (!io || !io->E || !io->x0 || !io->workspace)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_stage_adjoint: io, E, x0 and workspace are required");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_stage_adjoint")) return rc;
+    hipError_t e = rqp_ltv_launch_stage_adjoint(dims, nc, io, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_stage_adjoint: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
 const char* rqp_last_error(const rqp_handle* h) { return h ? h->err.c_str() : ltv_err.c_str(); }
 
 const char* rqp_version(void) { return RQP_VERSION; }

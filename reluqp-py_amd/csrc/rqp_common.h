@@ -346,6 +346,14 @@ hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const 
 hipError_t rqp_ltv_launch_vectors(const rqp_ltv_dims* d, const void* x0, const void* xref, const void* uref, const void* l_add,
                                   const void* u_add, const double* Q, const double* R, const double* Qf, const void* ws, void* g,
                                   void* l, void* u, hipStream_t s);
+// where F [B][m][n] and [G | f] [B][m][nx + 1] sit in the forward workspace (host side; for readers outside rqp_condense.hip)
+void rqp_ltv_ws_maps(const rqp_ltv_dims* d, const void* ws, const double** F, const double** Gf);
+// stage constraints on the forward workspace (rqp_stage.hip)
+const char* rqp_ltv_stage_check_size(const rqp_ltv_dims* d, int nc);       // RQP_ERR_UNSUPPORTED
+hipError_t rqp_ltv_launch_stage_rows(const rqp_ltv_dims* d, int nc, const void* E, const void* ws, void* Ac, hipStream_t s);
+hipError_t rqp_ltv_launch_stage_vectors(const rqp_ltv_dims* d, int nc, const void* E, const void* x0, const void* lo, const void* hi,
+                                        const void* ws, void* lc, void* uc, hipStream_t s);
+hipError_t rqp_ltv_launch_stage_adjoint(const rqp_ltv_dims* d, int nc, const rqp_ltv_stage_adjoint_io* io, hipStream_t s);
 // reverse mode of the condensing (rqp_condense_adj.hip)
 size_t rqp_ltv_adj_ws_bytes(const rqp_ltv_dims* d);
 hipError_t rqp_ltv_launch_condense_adjoint(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io, hipStream_t s);

@@ -387,6 +387,12 @@ size_t rqp_ltv_ws_bytes(const rqp_ltv_dims* d) {
     return sizeof(double) * B * (2 * m * n + m * nxa + n * nxa);
 }
 
+void rqp_ltv_ws_maps(const rqp_ltv_dims* d, const void* ws, const double** F, const double** Gf) {
+    const LtvArgs a = base_args(d, const_cast<void*>(ws));
+    *F = a.F;
+    *Gf = a.Gf;
+}
+
 hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
                                    const double* R, const double* Qf, const double* K, void* H, void* A, void* ws, hipStream_t s) {
     LtvArgs a = base_args(d, ws);

@@ -26,7 +26,7 @@ ABI_SYMBOLS = (
     "rqp_warm_start", "rqp_clear_primal_dual", "rqp_solve", "rqp_iterate", "rqp_compute_residuals",
     "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity",
     "rqp_ltv_workspace_bytes", "rqp_ltv_condense", "rqp_ltv_vectors", "rqp_ltv_adjoint_workspace_bytes",
-    "rqp_ltv_condense_adjoint", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
+    "rqp_ltv_condense_adjoint", "rqp_ltv_stage_rows", "rqp_ltv_stage_vectors", "rqp_ltv_stage_adjoint", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
     "rqp_last_error", "rqp_version",
 )
 
@@ -74,6 +74,7 @@ class SensitivityIO(ctypes.Structure):
 
 
 LTV_HAS_K, LTV_HAS_C, LTV_HAS_XREF, LTV_HAS_UREF, LTV_BOUNDS_BATCHED = 1, 2, 4, 8, 16     # RQP_LTV_* (rqp_ltv_dims.flags)
+LTV_STAGE_SHARED_E = 32                                                                   # (the rqp_ltv_stage_* calls only)
 
 
 class LtvDims(ctypes.Structure):
@@ -86,6 +87,11 @@ class LtvAdjointIO(ctypes.Structure):
     _fields_ = [(f, ctypes.c_void_p) for f in ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf", "K", "workspace",
                                                 "dH", "dA", "dg", "dl", "du", "dAd", "dBd", "dc", "dx0", "dxref", "duref",
                                                 "dQ", "dR", "dQf", "adjoint_workspace")]
+
+
+class LtvStageAdjointIO(ctypes.Structure):
+    """struct rqp_ltv_stage_adjoint_io: device pointers (None = NULL)."""
+    _fields_ = [(f, ctypes.c_void_p) for f in ("E", "x0", "workspace", "dA_c", "dl_c", "du_c", "dA_full", "dl_full", "dE")]
 
 
 class CInfo(ctypes.Structure):
@@ -148,6 +154,9 @@ def load():
         "rqp_ltv_vectors": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 13),
         "rqp_ltv_adjoint_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.POINTER(ctypes.c_size_t)]),
         "rqp_ltv_condense_adjoint": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, ctypes.POINTER(LtvAdjointIO), vp]),
+        "rqp_ltv_stage_rows": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, i32] + [vp] * 4),
+        "rqp_ltv_stage_vectors": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, i32] + [vp] * 8),
+        "rqp_ltv_stage_adjoint": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, i32, ctypes.POINTER(LtvStageAdjointIO), vp]),
         "rqp_kernel_name": (ctypes.c_char_p, [H]),
         "rqp_destroy": (ctypes.c_int, [H]),
         "rqp_strerror": (ctypes.c_char_p, [ctypes.c_int]),

@@ -164,26 +164,97 @@ class LTVCondenseFunction(torch.autograd.Function):
         return H, A, g, l, u
 
     @staticmethod
-    def backward(ctx, gH, gA, gg, gl, gu):
-        Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors
+    def restore(ctx):
+        """The forward workspace of this ctx's linearisation: condensed again from the saved inputs when a later forward has
+        overwritten it.  Returns (slot, weights)."""
+        Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors[:9]
         slot = ctx.slot
+        w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+        if slot["stamp"] != ctx.stamp:
+            Hs, As = ctx.condenser.recondense_outputs(slot, Ad.shape[0], Ad.device, Ad.dtype)
+            mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, H=Hs, A=As)
+            slot["stamp"] = ctx.stamp
+        return slot, w
+
+    @staticmethod
+    def reverse(ctx, gH, gA, gg, gl, gu, ninputs):
+        """The gradients of (Ad, Bd, c, x0, xref, uref, Q, R, Qf) -- inputs 1 .. 9 of ``forward`` -- that ``needs_input_grad``
+        names, in a list of ``ninputs`` entries (the others None)."""
+        Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors[:9]
         names = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
-        need = ctx.needs_input_grad
-        want = tuple(k for k, nd in zip(names, need[1:10]) if nd)
-        grads = [None] * 12
+        want = tuple(k for k, nd in zip(names, ctx.needs_input_grad[1:10]) if nd)
+        grads = [None] * ninputs
         if want:
-            w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
-            if slot["stamp"] != ctx.stamp:               # a later forward has overwritten the workspace: condense these stages again
-                Hs, As = ctx.condenser.recondense_outputs(slot, Ad.shape[0], Ad.device, Ad.dtype)
-                mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, H=Hs, A=As)
-                slot["stamp"] = ctx.stamp
+            slot, w = LTVCondenseFunction.restore(ctx)
             out = mpc.condense_ltv_adjoint_device(Ad, Bd, x0, w, slot["ws"], slot["adj"], xref=xref, uref=uref, dH=gH, dA=gA,
                                                   dg=gg, dl=gl, du=gu, want=want)
             qdt = dict(Q=ctx.meta[0], R=ctx.meta[1], Qf=ctx.meta[2])
             for i, k in enumerate(names):
                 if k in out:
                     grads[1 + i] = out[k].to(qdt[k]) if k in qdt else out[k]
+        return grads
+
+    @staticmethod
+    def backward(ctx, gH, gA, gg, gl, gu):
+        need = ctx.needs_input_grad
+        grads = LTVCondenseFunction.reverse(ctx, gH, gA, gg, gl, gu, 12)
         for i, gb, dim, dt in ((10, gl, ctx.meta[3], ctx.meta[5]), (11, gu, ctx.meta[4], ctx.meta[6])):
+            if need[i] and gb is not None:
+                grads[i] = (gb if dim == 2 else gb.sum(0)).to(dt)
+        return tuple(grads)
+
+
+class StageConstraintFunction(torch.autograd.Function):
+    """``StageConstraintFunction.apply(condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, E, lo, hi)`` -> ``(H, A_c, g, l_c, u_c)``:
+    the condensed QPs of a batch of LTV plants under stage constraints lo_k <= E_k [u_k ; x_{k+1}] <= hi_k (E [B, N, nc, nu + nx]
+    or shared [N, nc, nu + nx]; lo, hi [B, N nc] or [N nc]).  Forward: ``LTVCondenseFunction``'s condensing (H, g), then C-ABI
+    rqp_ltv_stage_rows + rqp_ltv_stage_vectors on its workspace.  Backward: rqp_ltv_stage_adjoint turns the cotangents of (A_c,
+    l_c, u_c) into dE and into the (dA, dl) that ``LTVCondenseFunction``'s reverse maps on to the plant; it shares that class's
+    workspace stamp, so a backward whose workspace a later forward has overwritten condenses its stages again first.  The
+    gradients of a shared E and of shared bounds are summed over the batch."""
+
+    @staticmethod
+    def forward(ctx, condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, E, lo, hi):
+        cd = condenser
+        dtype, device, B = Ad.dtype, Ad.device, Ad.shape[0]
+        slot = cd.slot(B, device, dtype)
+        f64 = lambda W: (0.5 * (W.detach() + W.detach().transpose(0, 1))).to(device=device, dtype=torch.float64).contiguous()
+        Qd, Rd, Qfd = f64(Q), f64(R), f64(Qf)
+        w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+        det = lambda t: None if t is None else t.detach().contiguous()
+        Ad, Bd, c, x0, xref, uref = (det(t) for t in (Ad, Bd, c, x0, xref, uref))
+        Ed = E.detach().to(device=device, dtype=dtype).contiguous()
+        slot["stamp"] = ctx.stamp = cd.next_stamp()
+        _, As = cd.recondense_outputs(slot, B, device, dtype)            # (A = F of the box is not an output here)
+        H, _ = mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, A=As)
+        if "box0" not in slot:
+            slot["box0"] = torch.zeros(cd.m, dtype=dtype, device=device)
+        g, _, _ = mpc.ltv_vectors_device((cd.nx, cd.nu, cd.horizon, cd.K is not None, c is not None), x0, slot["box0"],
+                                         slot["box0"], w, slot["ws"], xref=xref, uref=uref)
+        dims4 = (B, cd.nx, cd.nu, cd.horizon)
+        A_c = mpc.stage_rows_device(dims4, Ed, slot["ws"])
+        l_c, u_c = mpc.stage_vectors_device(dims4, Ed, x0, lo.detach(), hi.detach(), slot["ws"])
+        ctx.condenser, ctx.slot, ctx.dims4 = cd, slot, dims4
+        ctx.meta = (Q.dtype, R.dtype, Qf.dtype, E.dim(), lo.dim(), hi.dim(), E.dtype, lo.dtype, hi.dtype)
+        ctx.save_for_backward(Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd, Ed)
+        ctx.set_materialize_grads(False)
+        return H, A_c, g, l_c, u_c
+
+    @staticmethod
+    def backward(ctx, gH, gA, gg, gl, gu):
+        need = ctx.needs_input_grad
+        x0, Ed = ctx.saved_tensors[3], ctx.saved_tensors[9]
+        plant = any(need[1:10])
+        dA_full = dl_full = dE = None
+        if (gA is not None or gl is not None or gu is not None) and (plant or need[10]):
+            slot, _ = LTVCondenseFunction.restore(ctx)
+            want = (("dA_full", "dl_full") if plant else ()) + (("dE",) if need[10] else ())
+            out = mpc.stage_adjoint_device(ctx.dims4, Ed, x0, slot["ws"], dA_c=gA, dl_c=gl, du_c=gu, want=want)
+            dA_full, dl_full, dE = out.get("dA_full"), out.get("dl_full"), out.get("dE")
+        grads = LTVCondenseFunction.reverse(ctx, gH, dA_full, gg, dl_full, None, 13)
+        if dE is not None:
+            grads[10] = (dE if ctx.meta[3] == 4 else dE.sum(0)).to(ctx.meta[6])
+        for i, gb, dim, dt in ((11, gl, ctx.meta[4], ctx.meta[7]), (12, gu, ctx.meta[5], ctx.meta[8])):
             if need[i] and gb is not None:
                 grads[i] = (gb if dim == 2 else gb.sum(0)).to(dt)
         return tuple(grads)
@@ -195,17 +266,52 @@ class LTVMPCLayer(torch.nn.Module):
     ``ReLUQPLayer`` on per-instance matrices (``setup_kwargs`` are its keyword arguments; its defaults ``differentiable=True,
     polish=True``), and the first input is u0 = v[:, :nu] - x0 K' [B, nu]; v [B, n] is the whole QP solution.  Gradients flow to
     Ad, Bd, c, x0, xref, uref and to the weights Q, R, Qf (shared by the batch: summed over it).  The box |u| <= u_max,
-    |x| <= x_max and the gain K are constants of the layer."""
+    |x| <= x_max and the gain K are constants of the layer.
 
-    def __init__(self, nx, nu, horizon, u_max, x_max, K=None, **setup_kwargs):
+    ``LTVMPCLayer(nx, nu, horizon, K=None, stage_rows=nc)`` (no u_max, x_max) replaces the box by nc rows per stage, lo_k <=
+    E_k [u_k ; x_{k+1}] <= hi_k, given with every call: ``layer(Ad, Bd, x0, Q, R, Qf, ..., E=, lo=, hi=)`` with E [B, N, nc,
+    nu + nx] or shared [N, nc, nu + nx] and lo, hi [B, N nc] or [N nc] (``StageConstraintFunction``).  Gradients then also flow
+    to E, lo and hi (summed over the batch where the input is shared)."""
+
+    def __init__(self, nx, nu, horizon, u_max=None, x_max=None, K=None, stage_rows=None, **setup_kwargs):
         super().__init__()
         self.condenser = mpc.LTVCondenser(nx, nu, horizon, K=K)
         self.nx, self.nu, self.horizon = self.condenser.nx, self.condenser.nu, self.condenser.horizon
-        _, self.l_add, self.u_add = mpc.box_constraints(self.nx, self.nu, self.horizon, u_max, x_max)
+        self.stage_rows = None if stage_rows is None else int(stage_rows)
+        if self.stage_rows is not None:
+            if u_max is not None or x_max is not None:
+                raise ValueError("stage_rows replaces the box: u_max and x_max must be None (write the box as rows of E)")
+            mpc._stage_check_sizes(self.horizon, self.stage_rows)
+            self.l_add = self.u_add = None
+        else:
+            if u_max is None or x_max is None:
+                raise ValueError("u_max and x_max are required without stage_rows")
+            _, self.l_add, self.u_add = mpc.box_constraints(self.nx, self.nu, self.horizon, u_max, x_max)
         self.qp = ReLUQPLayer(**setup_kwargs)
         self._const = {}
 
-    def _check(self, Ad, Bd, x0, Q, R, Qf, c, xref, uref):
+    def _check_stage(self, B, dtype, device, E, lo, hi):
+        nc, N, blk = self.stage_rows, self.horizon, self.nx + self.nu
+        if nc is None:
+            if E is not None or lo is not None or hi is not None:
+                raise ValueError("E, lo, hi need LTVMPCLayer(stage_rows=nc)")
+            return
+        for name, t in (("E", E), ("lo", lo), ("hi", hi)):
+            if not torch.is_tensor(t):
+                raise ValueError("stage_rows: %s must be given as a torch tensor" % name)
+        if tuple(E.shape) not in ((B, N, nc, blk), (N, nc, blk)):
+            raise ValueError("E has shape %s, expected %s or %s" % (tuple(E.shape), (B, N, nc, blk), (N, nc, blk)))
+        for name, t in (("lo", lo), ("hi", hi)):
+            if tuple(t.shape) not in ((B, N * nc), (N * nc,)):
+                raise ValueError("%s has shape %s, expected %s or %s" % (name, tuple(t.shape), (B, N * nc), (N * nc,)))
+        if lo.dim() != hi.dim():
+            raise ValueError("lo and hi must both be [B, N nc] or both [N nc]")
+        if any(t.dtype != dtype for t in (E, lo, hi)):
+            raise ValueError("E, lo, hi must have the precision of Ad")
+        if any(t.device != device for t in (E, lo, hi)):
+            raise ValueError("E, lo, hi must be on the device of Ad (%s)" % device)
+
+    def _check(self, Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(None, None, None)):
         nx, nu, N = self.nx, self.nu, self.horizon
         for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("Q", Q), ("R", R), ("Qf", Qf)):
             if not torch.is_tensor(t):
@@ -226,18 +332,22 @@ class LTVMPCLayer(torch.nn.Module):
                 raise ValueError("%s must be symmetric" % name)
         if Ad.dtype not in (torch.float32, torch.float64) or any(t is not None and t.dtype != Ad.dtype for t in (Bd, x0, c, xref, uref)):
             raise ValueError("Ad, Bd, x0 (c, xref, uref) must share one precision, float32 or float64")
+        self._check_stage(B, Ad.dtype, Ad.device, *stage)
         if Ad.device.type != "cuda":
             raise _cabi.RqpUnavailable("LTVMPCLayer needs a HIP device; the MI355X build has no CPU path")
         return B
 
-    def forward(self, Ad, Bd, x0, Q, R, Qf, c=None, xref=None, uref=None):
-        self._check(Ad, Bd, x0, Q, R, Qf, c, xref, uref)
+    def forward(self, Ad, Bd, x0, Q, R, Qf, c=None, xref=None, uref=None, E=None, lo=None, hi=None):
+        B = self._check(Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(E, lo, hi))
         key = (str(Ad.device), Ad.dtype)
         if key not in self._const:
             t = lambda a: None if a is None else torch.as_tensor(a, dtype=Ad.dtype, device=Ad.device)
             self._const[key] = (t(self.l_add), t(self.u_add), t(self.condenser.K))
         l_add, u_add, K = self._const[key]
-        H, A, g, l, u = LTVCondenseFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add)
+        if self.stage_rows is None:
+            H, A, g, l, u = LTVCondenseFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add)
+        else:
+            H, A, g, l, u = StageConstraintFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, E, lo, hi)
         out = self.qp(H, g, A, l, u)
         v = out[0]
         u0 = v[:, :self.nu] if K is None else v[:, :self.nu] - x0 @ K.transpose(0, 1)

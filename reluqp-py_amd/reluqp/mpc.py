@@ -526,6 +526,82 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=No
                 l_add=lb, u_add=ub, K=Kb)
 
 
+# Stage constraints: instead of the box on y, stage k carries nc rows  lo_k <= E_k [u_k ; x_{k+1}] <= hi_k  (m_c = N nc rows).
+# With y = F v + s, s = G x0 + f:  A_c = E F (block row k = E_k F_k),  l_c = lo - E s,  u_c = hi - E s;  H and g are unchanged.
+# stage_constraints / stage_constraints_vjp are the host statements, stage_*_device the device calls (C-ABI rqp_ltv_stage_*).
+
+STAGE_LIMITS = dict(nc=32, m_c=640)                           # what the device kernels hold (rqp_abi.h)
+
+
+def _stage_check_sizes(N, nc):
+    L = STAGE_LIMITS
+    if nc < 1 or nc > L["nc"] or N * nc > L["m_c"]:
+        raise ValueError("unsupported stage constraints (horizon=%d, nc=%d): the device kernels hold 1 <= nc <= %d rows per "
+                         "stage and m_c = horizon nc <= %d" % (N, nc, L["nc"], L["m_c"]))
+
+
+def _stage_blocks(F, E):
+    N, nc, blk = E.shape
+    if F.shape[0] != N * blk:
+        raise ValueError("E has shape %s, expected [N, nc, nu + nx] with N (nu + nx) = %d" % (tuple(E.shape), F.shape[0]))
+    return N, nc, blk
+
+
+def stage_constraints(cond, E, x0, lo, hi):
+    """(A_c, l_c, u_c) of the stage constraints lo_k <= E_k [u_k ; x_{k+1}] <= hi_k on the maps of ``condense_ltv`` (numpy, the
+    formulas as written above).  One instance: E [N, nc, nu + nx], x0 [nx], lo, hi [N nc]; or ``cond`` with a batch axis, x0
+    [B, nx], E with or without it (shared), lo / hi [B, N nc] or shared [N nc]."""
+    F, G, f = cond["F"], cond["G"], cond["f"]
+    E, x0 = np.asarray(E).astype(F.dtype), np.asarray(x0).astype(F.dtype)
+    if F.ndim == 3:
+        outs = [stage_constraints({k: (v if k == "H_sp" else v[b]) for k, v in cond.items()}, E[b] if E.ndim == 4 else E, x0[b],
+                                  np.asarray(lo)[b] if np.ndim(lo) == 2 else lo, np.asarray(hi)[b] if np.ndim(hi) == 2 else hi)
+                for b in range(F.shape[0])]
+        return tuple(np.stack([o[i] for o in outs]) for i in range(3))
+    if E.ndim != 3:
+        raise ValueError("E has shape %s, expected [N, nc, nu + nx]" % (tuple(E.shape),))
+    N, nc, blk = _stage_blocks(F, E)
+    lo, hi = np.asarray(lo).astype(F.dtype), np.asarray(hi).astype(F.dtype)
+    if lo.shape != (N * nc,) or hi.shape != (N * nc,):
+        raise ValueError("lo, hi have shapes %s, %s, expected (%d,)" % (lo.shape, hi.shape, N * nc))
+    s = G @ x0 + f
+    A_c = np.concatenate([E[k] @ F[k * blk:(k + 1) * blk] for k in range(N)])
+    Es = np.concatenate([E[k] @ s[k * blk:(k + 1) * blk] for k in range(N)])
+    return A_c, lo - Es, hi - Es
+
+
+def stage_constraints_vjp(cond, E, x0, dA_c=None, dl_c=None, du_c=None):
+    """Reverse of ``stage_constraints`` (numpy): the cotangents dA_c [N nc, n], dl_c, du_c [N nc] (an absent one is zero)
+    mapped to (dA_full [m, n], dl_full [m], dE [N, nc, nu + nx], dlo, dhi).  With t = dl_c + du_c:
+        dA_full_k = E_k' dA_c,k,   dl_full_k = E_k' t_k,   dE_k = dA_c,k F_k' - t_k s_k',   dlo = dl_c,   dhi = du_c.
+    dA_full and dl_full are the ``dA`` and ``dl`` of ``condense_ltv_vjp`` (``du=None`` there), which maps them on to the plant.
+    With a batch axis on ``cond``: everything per instance; dE is summed over the batch when E is shared, dlo / dhi stay per
+    instance (the sum for shared bounds is the caller's)."""
+    F, G, f = cond["F"], cond["G"], cond["f"]
+    E, x0 = np.asarray(E).astype(F.dtype), np.asarray(x0).astype(F.dtype)
+    if F.ndim == 3:
+        at = lambda a, b: None if a is None else np.asarray(a)[b]
+        outs = [stage_constraints_vjp({k: (v if k == "H_sp" else v[b]) for k, v in cond.items()}, E[b] if E.ndim == 4 else E,
+                                      x0[b], at(dA_c, b), at(dl_c, b), at(du_c, b)) for b in range(F.shape[0])]
+        res = [np.stack([o[i] for o in outs]) for i in range(5)]
+        if E.ndim == 3:
+            res[2] = res[2].sum(0)
+        return tuple(res)
+    N, nc, blk = _stage_blocks(F, E)
+    n = F.shape[1]
+    cast = lambda a, shape: np.zeros(shape, dtype=F.dtype) if a is None else np.asarray(a).astype(F.dtype).reshape(shape)
+    Ab, lb, ub = cast(dA_c, (N * nc, n)), cast(dl_c, (N * nc,)), cast(du_c, (N * nc,))
+    t = lb + ub
+    s = G @ x0 + f
+    dA_full, dl_full, dE = np.zeros_like(F), np.zeros_like(f), np.zeros_like(E)
+    for k in range(N):
+        rk, ck = slice(k * blk, (k + 1) * blk), slice(k * nc, (k + 1) * nc)
+        dA_full[rk] = E[k].T @ Ab[ck]
+        dl_full[rk] = E[k].T @ t[ck]
+        dE[k] = Ab[ck] @ F[rk].T - np.outer(t[ck], s[rk])
+    return dA_full, dl_full, dE, lb, ub
+
+
 class _LtvWeights(object):
     """Q, R, Qf (and K) as float64 device tensors (what the C-ABI reads), cached per device."""
 
@@ -769,6 +845,103 @@ def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, u
     return g, l, u
 
 
+def _stage_call(dims4, E, what):
+    """Common front of the stage_*_device wrappers: (lib, LtvDims without the bounds flag, nc, E, dtype, device)."""
+    import torch
+    from reluqp import _cabi
+    B, nx, nu, N = (int(v) for v in dims4)
+    _ltv_check_sizes(nx, nu, N)
+    if not torch.is_tensor(E):
+        raise ValueError("E must be a torch tensor")
+    dtype, device = E.dtype, E.device
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("E must be float32 or float64")
+    if E.dim() not in (3, 4) or tuple(E.shape[-3::2]) != (N, nu + nx) or (E.dim() == 4 and E.shape[0] != B):
+        raise ValueError("E has shape %s, expected [%d, nc, %d] or [%d, %d, nc, %d]" % (tuple(E.shape), N, nu + nx, B, N, nu + nx))
+    nc = int(E.shape[-2])
+    _stage_check_sizes(N, nc)
+    if device.type != "cuda":
+        raise _cabi.RqpUnavailable("%s needs device tensors; the host restatement is stage_constraints%s"
+                                   % (what, "_vjp" if "adjoint" in what else ""))
+    dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
+                         flags=_cabi.LTV_STAGE_SHARED_E if E.dim() == 3 else 0)
+    return _cabi.load(), dims, nc, E.contiguous(), dtype, device
+
+
+def stage_rows_device(dims4, E, workspace, A_c=None):
+    """A_c = E F [B, N nc, n] from the workspace of the last ``condense_ltv_device`` (C-ABI rqp_ltv_stage_rows).  ``dims4`` =
+    (B, nx, nu, horizon) of that call; E [B, N, nc, nu + nx] or shared [N, nc, nu + nx], a device tensor of the output
+    precision.  Enqueued on the current stream; returns A_c (its entries right of the staircase are exact zeros)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    lib, dims, nc, E, dtype, device = _stage_call(dims4, E, "stage_rows_device")
+    A_c = _ltv_out(A_c, (dims.batch, dims.horizon * nc, dims.horizon * dims.nu), dtype, device, "A_c")
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_stage_rows(ctypes.byref(dims), device.index or 0, nc, _cabi.ptr(E), _cabi.ptr(workspace),
+                                                 _cabi.ptr(A_c), stream), "rqp_ltv_stage_rows", handleless=True)
+    return A_c
+
+
+def stage_vectors_device(dims4, E, x0, lo, hi, workspace, l_c=None, u_c=None):
+    """l_c = lo - E s, u_c = hi - E s [B, N nc] with s = G x0 + f of the workspace (C-ABI rqp_ltv_stage_vectors).  x0 [B, nx];
+    lo, hi [N nc] or [B, N nc] (infinite entries stay infinite).  Enqueued on the current stream; returns (l_c, u_c)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    lib, dims, nc, E, dtype, device = _stage_call(dims4, E, "stage_vectors_device")
+    B, mc = dims.batch, dims.horizon * nc
+    x0 = _ltv_in(x0, (B, dims.nx), dtype, device, "x0")
+    batched = torch.as_tensor(lo).dim() == 2
+    lo = _ltv_in(lo, (B, mc) if batched else (mc,), dtype, device, "lo")
+    hi = _ltv_in(hi, (B, mc) if batched else (mc,), dtype, device, "hi")
+    if batched:
+        dims.flags |= _cabi.LTV_BOUNDS_BATCHED
+    l_c, u_c = _ltv_out(l_c, (B, mc), dtype, device, "l_c"), _ltv_out(u_c, (B, mc), dtype, device, "u_c")
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_stage_vectors(ctypes.byref(dims), device.index or 0, nc, _cabi.ptr(E), _cabi.ptr(x0),
+                                                    _cabi.ptr(lo), _cabi.ptr(hi), _cabi.ptr(workspace), _cabi.ptr(l_c),
+                                                    _cabi.ptr(u_c), stream), "rqp_ltv_stage_vectors", handleless=True)
+    return l_c, u_c
+
+
+STAGE_ADJOINT_OUTPUTS = ("dA_full", "dl_full", "dE")
+
+
+def stage_adjoint_device(dims4, E, x0, workspace, dA_c=None, dl_c=None, du_c=None, want=STAGE_ADJOINT_OUTPUTS, out=None):
+    """Reverse of ``stage_rows_device`` + ``stage_vectors_device`` (C-ABI rqp_ltv_stage_adjoint; the host statement is
+    ``stage_constraints_vjp``).  ``workspace`` is the forward workspace of this linearisation; dA_c [B, N nc, n], dl_c, du_c
+    [B, N nc] are the cotangents (None = zero).  Returns a dict of the outputs ``want`` names: dA_full [B, m, n] and dl_full
+    [B, m] (the ``dA``, ``dl`` of ``condense_ltv_adjoint_device``), dE [B, N, nc, nu + nx] (per instance also for a shared E).
+    ``out``: optional dict of tensors to write into.  Enqueued on the current stream."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    lib, dims, nc, E, dtype, device = _stage_call(dims4, E, "stage_adjoint_device")
+    unknown = [k for k in want if k not in STAGE_ADJOINT_OUTPUTS]
+    if unknown:
+        raise ValueError("unknown output name(s) %s; known: %s" % (unknown, STAGE_ADJOINT_OUTPUTS))
+    B, N, nx, nu = dims.batch, dims.horizon, dims.nx, dims.nu
+    n, m, mc = N * nu, N * (nx + nu), N * nc
+    x0 = _ltv_in(x0, (B, nx), dtype, device, "x0")
+    opt = lambda t, shape, name: None if t is None else _ltv_in(t, shape, dtype, device, name)
+    dA_c, dl_c, du_c = opt(dA_c, (B, mc, n), "dA_c"), opt(dl_c, (B, mc), "dl_c"), opt(du_c, (B, mc), "du_c")
+    shapes = dict(dA_full=(B, m, n), dl_full=(B, m), dE=(B, N, nc, nu + nx))
+    res = {k: _ltv_out(None if out is None else out.get(k), shapes[k], dtype, device, k) for k in want}
+    io = _cabi.LtvStageAdjointIO()
+    for name, t in (("E", E), ("x0", x0), ("workspace", workspace), ("dA_c", dA_c), ("dl_c", dl_c), ("du_c", du_c)):
+        setattr(io, name, None if t is None else t.data_ptr())
+    for k, t in res.items():
+        setattr(io, k, t.data_ptr())
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_stage_adjoint(ctypes.byref(dims), device.index or 0, nc, ctypes.byref(io), stream),
+                    "rqp_ltv_stage_adjoint", handleless=True)
+    return res
+
+
 class BatchedLTVMPC(object):
     """Closed-loop MPC on a batch of plants that each have their own, time-varying linearisation.
 
@@ -777,13 +950,28 @@ class BatchedLTVMPC(object):
     (g, l, u) for the current states on the device, ``update(g, l, u)``, warm-started ``solve()``, and returns the first input
     u_0 = v_0 - K x [B, nu] (a device tensor) and the ``Results``.  Weights Q, R, Qf and the pre-stabilising gain K are shared
     by the batch; the box |u| <= u_max, |x| <= x_max is ``box_constraints``.  Only the solver's public setup / update /
-    solve are called, so every solver option (``precision``, ``polish``, ``sensitivity``, ``devices`` ...) works unchanged."""
+    solve are called, so every solver option (``precision``, ``polish``, ``sensitivity``, ``devices`` ...) works unchanged.
 
-    def __init__(self, nx, nu, horizon, Q, R, Qf, u_max, x_max, K=None, solver=None, **solver_kw):
+    ``stage_rows=nc`` replaces the box by nc rows per stage, lo_k <= E_k [u_k ; x_{k+1}] <= hi_k (``stage_constraints``;
+    u_max and x_max must then be None): ``linearize(Ad, Bd, c=None, E=None)`` takes E [B, N, nc, nu + nx] or shared [N, nc,
+    nu + nx] and ``step(x, ..., lo=None, hi=None)`` the bounds [B, N nc] or [N nc]; each is required on first use and kept
+    until replaced.  The QPs then have ``m = N nc`` rows (A_c = E F is built on the device, rqp_ltv_stage_rows)."""
+
+    def __init__(self, nx, nu, horizon, Q, R, Qf, u_max=None, x_max=None, K=None, solver=None, stage_rows=None, **solver_kw):
         nx, nu, horizon = int(nx), int(nu), int(horizon)
         _ltv_check_sizes(nx, nu, horizon)
         self.nx, self.nu, self.horizon = nx, nu, horizon
         self.n, self.m = horizon * nu, horizon * (nx + nu)
+        self.stage_rows = None if stage_rows is None else int(stage_rows)
+        if self.stage_rows is not None:
+            if u_max is not None or x_max is not None:
+                raise ValueError("stage_rows replaces the box: u_max and x_max must be None (write the box as rows of E)")
+            _stage_check_sizes(horizon, self.stage_rows)
+            self.m_box, self.m = self.m, horizon * self.stage_rows
+            u_max = x_max = 0.0                # (the box vectors only feed the scratch l, u of rqp_ltv_vectors)
+        elif u_max is None or x_max is None:
+            raise ValueError("u_max and x_max are required without stage_rows")
+        self._E = self._lo = self._hi = None
         self.weights = _LtvWeights(nx, nu, Q, R, Qf, K)
         self.K = self.weights.K
         _, l_add, u_add = box_constraints(nx, nu, horizon, u_max, x_max)
@@ -816,7 +1004,16 @@ class BatchedLTVMPC(object):
                              l_add=torch.as_tensor(self.l_add, dtype=dtype, device=device),
                              u_add=torch.as_tensor(self.u_add, dtype=dtype, device=device),
                              Kt=None if self.K is None else torch.as_tensor(self.K.T.copy(), dtype=dtype, device=device))
+            if self.stage_rows is not None:    # what rqp_ltv_condense / rqp_ltv_vectors write besides H and g: A = F, the box l, u
+                self._buf.update(A_box=e(B, self.m_box, self.n), l_box=e(B, self.m_box), u_box=e(B, self.m_box))
         return self._buf
+
+    def _stage_input(self, t, shapes, name, device, dtype):
+        import torch
+        t = torch.as_tensor(t).to(device=device, dtype=dtype).contiguous()
+        if tuple(t.shape) not in shapes:
+            raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), " or ".join(str(s) for s in shapes)))
+        return t
 
     def _handover(self, device):
         """devices=[...]: the shards run on their own streams, so what this stream built must be complete first."""
@@ -824,9 +1021,10 @@ class BatchedLTVMPC(object):
         if self.solver_kw.get("devices"):
             torch.cuda.current_stream(device).synchronize()
 
-    def linearize(self, Ad, Bd, c=None):
+    def linearize(self, Ad, Bd, c=None, E=None):
         """New stage matrices Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]): H and A of every instance are rebuilt on the
-        device; the solver is set up on the first ``step`` (it needs g, l, u) and re-factored, state kept, afterwards."""
+        device; the solver is set up on the first ``step`` (it needs g, l, u) and re-factored, state kept, afterwards.
+        With ``stage_rows``: E [B, N, nc, nu + nx] or [N, nc, nu + nx], kept until replaced."""
         import torch
         from reluqp import _cabi
         B, N, nx, nu = _ltv_shapes(Ad, Bd)
@@ -834,21 +1032,41 @@ class BatchedLTVMPC(object):
             raise ValueError("stages of shape (N=%d, nx=%d, nu=%d), expected (%d, %d, %d)" % (N, nx, nu, self.horizon, self.nx, self.nu))
         if c is not None and tuple(c.shape) != (B, N, nx):
             raise ValueError("c has shape %s, expected %s" % (tuple(c.shape), (B, N, nx)))
+        nc = self.stage_rows
+        if nc is None and E is not None:
+            raise ValueError("E needs BatchedLTVMPC(stage_rows=nc)")
+        if nc is not None:
+            if E is None and self._E is None:
+                raise ValueError("stage_rows: the first linearize() needs E")
+            if E is not None:
+                blk = nx + nu
+                if tuple(E.shape) not in ((B, N, nc, blk), (N, nc, blk)):
+                    raise ValueError("E has shape %s, expected %s or %s" % (tuple(E.shape), (B, N, nc, blk), (N, nc, blk)))
+            elif self._E.dim() == 4 and self._E.shape[0] != B:
+                raise ValueError("the kept E is for a batch of %d, the stages for %d" % (self._E.shape[0], B))
         if not torch.cuda.is_available():
             raise _cabi.RqpUnavailable("BatchedLTVMPC needs a HIP device; the MI355X build has no CPU path")
         device, dtype = self._place()
         buf = self._buffers(B, device, dtype)
         to = lambda t: torch.as_tensor(t).to(device=device, dtype=dtype)
-        condense_ltv_device(to(Ad), to(Bd), self.weights, buf["ws"], c=None if c is None else to(c), H=buf["H"], A=buf["A"])
+        condense_ltv_device(to(Ad), to(Bd), self.weights, buf["ws"], c=None if c is None else to(c), H=buf["H"],
+                            A=buf["A"] if nc is None else buf["A_box"])
+        if nc is not None:
+            if E is not None:
+                self._E = to(E).contiguous()
+            stage_rows_device((B, nx, nu, N), self._E, buf["ws"], A_c=buf["A"])
         self._lin = (c is not None,)
         if self._ready:
             self._handover(device)
             self.solver.update(Hx=buf["H"], Ax=buf["A"])
         return None
 
-    def qp_vectors(self, x, xref=None, uref=None):
-        """(g, l, u) device tensors of the QPs for the states x [B, nx] under the current linearisation."""
+    def qp_vectors(self, x, xref=None, uref=None, lo=None, hi=None):
+        """(g, l, u) device tensors of the QPs for the states x [B, nx] under the current linearisation (``stage_rows``: with
+        the bounds lo, hi [B, N nc] or [N nc], kept until replaced)."""
         import torch
+        if self.stage_rows is not None and ((lo is None and self._lo is None) or (hi is None and self._hi is None)):
+            raise ValueError("stage_rows: the first step() needs lo and hi")
         if self._lin is None:
             raise RuntimeError("BatchedLTVMPC: linearize() first")
         device, dtype = self._place()
@@ -857,15 +1075,30 @@ class BatchedLTVMPC(object):
         x = to(x)
         if tuple(x.shape) != (buf["B"], self.nx):
             raise ValueError("x has shape %s, expected %s" % (tuple(x.shape), (buf["B"], self.nx)))
-        return ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
-                                  buf["u_add"], self.weights, buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"], l=buf["l"],
-                                  u=buf["u"])
+        nc = self.stage_rows
+        if nc is None:
+            if lo is not None or hi is not None:
+                raise ValueError("lo, hi need BatchedLTVMPC(stage_rows=nc)")
+            return ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
+                                      buf["u_add"], self.weights, buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"], l=buf["l"],
+                                      u=buf["u"])
+        for name, t in (("lo", lo), ("hi", hi)):
+            if t is not None:
+                setattr(self, "_" + name, self._stage_input(t, ((buf["B"], self.m), (self.m,)), name, device, dtype))
+        if self._lo.dim() != self._hi.dim():
+            raise ValueError("lo and hi must both be [B, N nc] or both [N nc]")
+        g, _, _ = ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
+                                     buf["u_add"], self.weights, buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"],
+                                     l=buf["l_box"], u=buf["u_box"])
+        l, u = stage_vectors_device((buf["B"], self.nx, self.nu, self.horizon), self._E, x, self._lo, self._hi, buf["ws"],
+                                    l_c=buf["l"], u_c=buf["u"])
+        return g, l, u
 
-    def step(self, x, xref=None, uref=None):
-        """One control step for the states x [B, nx] (references xref [B, N, nx] for x_1 .. x_N, uref [B, N, nu]):
-        returns (u_0 [B, nu] device tensor, Results)."""
+    def step(self, x, xref=None, uref=None, lo=None, hi=None):
+        """One control step for the states x [B, nx] (references xref [B, N, nx] for x_1 .. x_N, uref [B, N, nu]; with
+        ``stage_rows`` the bounds lo, hi): returns (u_0 [B, nu] device tensor, Results)."""
         import torch
-        g, l, u = self.qp_vectors(x, xref, uref)
+        g, l, u = self.qp_vectors(x, xref, uref, lo, hi)
         device, dtype = self._place()
         buf = self._buf
         self._handover(device)

@@ -7,9 +7,12 @@ warm-started solve() of the handle set up on that data, in the same run; then th
 mode (condense_ltv_adjoint_device, rqp_ltv_condense_adjoint: every cotangent given, every gradient wanted) next to the forward
 `condense` and to adjoint() of a differentiable handle set up on the same data.  The host path it replaces -- numpy condense_ltv
 over the batch on --workers processes plus the host-to-device copy of (H, A) -- is timed on --host-batch instances and
-scaled to B.  Per-kernel times: run the same command under `rocprofv3 --kernel-trace --stats`.
+scaled to B.  Stage columns (--stage-rows nc, default 6 -> m_c = 120): rqp_ltv_stage_rows, rqp_ltv_stage_vectors and
+rqp_ltv_stage_adjoint next to `condense`, and update(Hx, Ax) + warm solve() of a BatchedLTVMPC(stage_rows=nc) handle (the input
+box as nu rows of E plus nc - nu random half-planes per stage) next to the same two of the box handle at m = 320.
+Per-kernel times (k_ltv_transition among them): run the same command under `rocprofv3 --kernel-trace --stats`.
 
-    python tools/ltv_bench.py [--reps 20] [--out profiles/r8_ltv/ltv_bench.json]
+    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--out profiles/r8_ltv/ltv_bench.json] [--stage-out profiles/r10_ltv_stage/ltv_stage_bench.json]
 """
 import argparse
 import json
@@ -63,8 +66,13 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--workers", type=int, default=16)
     ap.add_argument("--host-batch", type=int, default=256)
+    ap.add_argument("--stage-rows", type=int, default=6)
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r8_ltv", "ltv_bench.json"))
+    ap.add_argument("--stage-out", default=os.path.join(REPO, "profiles", "r10_ltv_stage", "ltv_stage_bench.json"),
+                    help="where the stage columns go, next to the condense / update / solve columns of the same run")
     args = ap.parse_args()
+    if not NU <= args.stage_rows <= 32:
+        ap.error("--stage-rows must be in [%d, 32]: the input box takes %d rows of E, the kernels hold 32" % (NU, NU))
     B = args.batch
     Ad0, Bd0 = mpc.random_plant(NX, NU, seed=0)
     Q, R = np.eye(NX), 0.1 * np.eye(NU)
@@ -120,6 +128,42 @@ def main():
         out["qp_adjoint_ms"], _, _ = _timed(torch, lambda: sd.adjoint(dx), args.reps)
         del sd
         out["condense_adjoint_over_condense"] = out["condense_adjoint_ms"] / out["condense_ms"]
+        # stage constraints on the same workspace: nc rows per stage, the input box as rows of E plus half-planes on the state
+        nc, blk = args.stage_rows, NX + NU
+        Eh = np.zeros((B, N, nc, blk))
+        Eh[:, :, :NU, :NU] = np.eye(NU)
+        Eh[:, :, NU:, NU:] = rs.randn(B, N, nc - NU, NX) / np.sqrt(NX)
+        lo_h = np.tile(np.hstack([np.full(NU, -0.4), np.full(nc - NU, -8.0)]), N)
+        Et, lot, hit = t(Eh), t(lo_h), t(-lo_h)
+        d4 = (B, NX, NU, N)
+        sb = dict(A_c=torch.empty(B, N * nc, ctl.n, dtype=prec, device=dev), l_c=torch.empty(B, N * nc, dtype=prec, device=dev),
+                  u_c=torch.empty(B, N * nc, dtype=prec, device=dev))
+        out["stage_rows"], out["m_c"] = nc, N * nc
+        out["stage_rows_ms"], out["stage_rows_min_ms"], out["stage_rows_max_ms"] = _timed(
+            torch, lambda: mpc.stage_rows_device(d4, Et, buf["ws"], A_c=sb["A_c"]), args.reps)
+        out["stage_vectors_ms"], _, _ = _timed(
+            torch, lambda: mpc.stage_vectors_device(d4, Et, xt, lot, hit, buf["ws"], l_c=sb["l_c"], u_c=sb["u_c"]), args.reps)
+        scot = [t(rs.randn(B, N * nc, ctl.n)), t(rs.randn(B, N * nc)), t(rs.randn(B, N * nc))]
+        sout = {k: torch.empty(sh, dtype=prec, device=dev) for k, sh in
+                (("dA_full", (B, ctl.m, ctl.n)), ("dl_full", (B, ctl.m)), ("dE", (B, N, nc, blk)))}
+        out["stage_adjoint_ms"], out["stage_adjoint_min_ms"], out["stage_adjoint_max_ms"] = _timed(
+            torch, lambda: mpc.stage_adjoint_device(d4, Et, xt, buf["ws"], *scot, out=sout), args.reps)
+        out["stage_rows_over_condense"] = out["stage_rows_ms"] / out["condense_ms"]
+        del scot, sout, sb
+        sctl = mpc.BatchedLTVMPC(NX, NU, N, Q, R, P, K=K, stage_rows=nc, device=dev, precision=prec, eps_abs=1e-3)
+        sctl.linearize(Adt, Bdt, E=Et)
+        sctl.step(xt, lo=lot, hi=hit)
+        ss, sbuf = sctl.solver, sctl._buf
+        out["stage_kernel"] = ss.kernel
+        ss.synchronous = False
+        out["stage_update_mats_ms"], _, _ = _timed(torch, lambda: ss.update(Hx=sbuf["H"], Ax=sbuf["A"]), args.reps)
+        sctl.qp_vectors(xt)
+
+        def stage_warm_solve():
+            ss.update(g=sbuf["g"], l=sbuf["l"], u=sbuf["u"])
+            ss.solve()
+        out["stage_warm_solve_ms"], _, _ = _timed(torch, stage_warm_solve, args.reps)
+        del sctl, ss, sbuf, Et
         del adj_ws, cot
         torch.cuda.synchronize()
         out["condense_over_update_mats"] = out["condense_ms"] / out["update_mats_ms"]
@@ -138,6 +182,13 @@ def main():
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(dict(device=torch.cuda.get_device_name(0), results=res), f, indent=1)
+    # the stage figures with what they are read against, in a file of their own
+    keep = ("batch", "nx", "nu", "horizon", "n", "m", "dtype", "kernel", "reps", "condense_ms", "condense_min_ms", "condense_max_ms",
+            "vectors_ms", "update_mats_ms", "warm_solve_ms", "condense_adjoint_ms")
+    stage = [{k: v for k, v in r.items() if k in keep or k.startswith("stage_") or k == "m_c"} for r in res]
+    os.makedirs(os.path.dirname(args.stage_out), exist_ok=True)
+    with open(args.stage_out, "w") as f:
+        json.dump(dict(device=torch.cuda.get_device_name(0), results=stage), f, indent=1)
 
 
 if __name__ == "__main__":
