@@ -414,12 +414,22 @@ int rqp_sensitivity(rqp_handle* h, const rqp_sensitivity_io* io, void* stream);
  * (rqp_ltv_workspace_bytes) belongs to the caller and carries F, H_sp F, [G | f] and F' H_sp [G | f] from rqp_ltv_condense to
  * any number of rqp_ltv_vectors calls.  Sizes: nx <= 16, nu <= 8, horizon <= 32, n <= 160, m <= 640, else
  * RQP_ERR_UNSUPPORTED.  A failure's text: rqp_last_error(NULL) (per host thread, cleared at the entry of each rqp_ltv_* call).
- * The calling thread's current HIP device is the same after the call as before it.                                           */
+ * The calling thread's current HIP device is the same after the call as before it.
+ *
+ * Stage weights (DESIGN.md section 5 "LTV condensing, stage weights"): with RQP_LTV_STAGE_WEIGHTS the cost is per instance and
+ * per stage, H_sp = blkdiag(R_0, Q_0, R_1, Q_1, ..., R_{N-1}, Q_{N-1}) of instance b: R_k weighs u_k, Q_k weighs x_{k+1}, so
+ * Q_{N-1} is the terminal weight.  Q is then [batch][horizon][nx][nx] and R [batch][horizon][nu][nu] (DEVICE, double, every block
+ * symmetric: read as given), Qf is not read and may be NULL.  rqp_ltv_condense, rqp_ltv_vectors (for H_sp yref) and
+ * rqp_ltv_condense_adjoint honour the flag, and a workspace must be read with the flag it was written with; the workspace sizes
+ * do not depend on it; the rqp_ltv_stage_* calls read only the workspace, accept the flag and ignore it.  Without the flag
+ * nothing changes: the same kernels, the same bits.  Repeated blocks (Q_k = Q, Q_{N-1} = Qf, R_k = R) give the bits of the
+ * shared call.                                                                                                               */
 #define RQP_LTV_HAS_K 1            /* K is given (else K = 0)                                              */
 #define RQP_LTV_HAS_C 2            /* c [batch][horizon][nx] is given (else c = 0)                         */
 #define RQP_LTV_HAS_XREF 4         /* rqp_ltv_vectors: xref [batch][horizon][nx] (x_1 .. x_N) is given     */
 #define RQP_LTV_HAS_UREF 8         /* rqp_ltv_vectors: uref [batch][horizon][nu] is given                  */
 #define RQP_LTV_BOUNDS_BATCHED 16  /* l_add, u_add are [batch][m] (else [m], shared)                       */
+#define RQP_LTV_STAGE_WEIGHTS 128  /* Q is [batch][horizon][nx][nx], R [batch][horizon][nu][nu] (double); Qf is not read */
 typedef struct rqp_ltv_dims {
     int32_t batch, nx, nu, horizon;
     int32_t dtype;               /* rqp_dtype of the batched inputs and of every output                  */
@@ -460,6 +470,8 @@ typedef struct rqp_ltv_adjoint_io {
     void *dAd, *dBd, *dc;        /* outputs [batch][horizon][nx][nx], [..][nx][nu], [..][nx]; NULL = not wanted          */
     void *dx0, *dxref, *duref;   /* outputs shaped like x0, xref, uref; NULL = not wanted                                */
     double *dQ, *dR, *dQf;       /* outputs [nx][nx], [nu][nu], [nx][nx], summed over the batch, symmetric; NULL = not wanted */
+                                 /* RQP_LTV_STAGE_WEIGHTS: dQ [batch][horizon][nx][nx], dR [batch][horizon][nu][nu], each block  */
+                                 /* the symmetrised Sb_kk block of its own instance and stage, no batch sum; dQf must be NULL    */
     void* adjoint_workspace;     /* rqp_ltv_adjoint_workspace_bytes, the caller's; contents need not survive the call    */
 } rqp_ltv_adjoint_io;
 
@@ -471,8 +483,9 @@ int rqp_ltv_adjoint_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes);
  * `stream` of `device` with no allocation and no host synchronisation, a fixed launch chain that depends on dims and on which
  * pointers are NULL only (capturable in a HIP graph), the caller's current device restored.  Work that only serves outputs that
  * are not wanted is skipped (dx0 / dxref / duref alone: one kernel; no dAd, dBd, dc: no sweep).  No atomics: the batch sums of
- * dQ, dR, dQf are added in a fixed order and two calls give the same bits.  RQP_ERR_ARG: io, Ad, Bd, x0, Q, R, Qf, workspace or
- * adjoint_workspace NULL, or a flag names an input whose pointer is NULL.                                                  */
+ * dQ, dR, dQf are added in a fixed order and two calls give the same bits (RQP_LTV_STAGE_WEIGHTS: there is no sum, one kernel
+ * symmetrises the per-stage blocks into dQ, dR).  RQP_ERR_ARG: io, Ad, Bd, x0, Q, R, Qf (without RQP_LTV_STAGE_WEIGHTS),
+ * workspace or adjoint_workspace NULL, a flag names an input whose pointer is NULL, or dQf given with RQP_LTV_STAGE_WEIGHTS. */
 int rqp_ltv_condense_adjoint(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io, void* stream);
 
 /* ---- Stage constraints of LTV MPC problems (DESIGN.md section 5 "LTV condensing, stage constraints") ----

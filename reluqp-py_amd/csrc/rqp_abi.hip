@@ -1131,7 +1131,8 @@ int rqp_ltv_condense(const rqp_ltv_dims* dims, int device, const void* Ad, const
                      const double* R, const double* Qf, const double* K, void* H, void* A, void* workspace, void* stream) {
     ltv_err.clear();
     if (int rc = ltv_check(dims, "rqp_ltv_condense")) return rc;
-    if (!Ad || !Bd || !Q || !R || !Qf || !H || !A || !workspace)
+    const bool staged = (dims->flags & RQP_LTV_STAGE_WEIGHTS) != 0;      // Q, R per (instance, stage); Qf is not read
+    if (!Ad || !Bd || !Q || !R || (!Qf && !staged) || !H || !A || !workspace)
         return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense: Ad, Bd, Q, R, Qf, H, A and workspace are required");
     if (((dims->flags & RQP_LTV_HAS_K) && !K) || ((dims->flags & RQP_LTV_HAS_C) && !c))
         return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense: a flag names an input whose pointer is NULL");
@@ -1147,7 +1148,8 @@ int rqp_ltv_vectors(const rqp_ltv_dims* dims, int device, const void* x0, const 
                     void* u, void* stream) {
     ltv_err.clear();
     if (int rc = ltv_check(dims, "rqp_ltv_vectors")) return rc;
-    if (!x0 || !l_add || !u_add || !Q || !R || !Qf || !workspace || !g || !l || !u)
+    const bool staged = (dims->flags & RQP_LTV_STAGE_WEIGHTS) != 0;
+    if (!x0 || !l_add || !u_add || !Q || !R || (!Qf && !staged) || !workspace || !g || !l || !u)
         return ltv_fail(RQP_ERR_ARG, "rqp_ltv_vectors: x0, l_add, u_add, Q, R, Qf, workspace, g, l and u are required");
     if (((dims->flags & RQP_LTV_HAS_XREF) && !xref) || ((dims->flags & RQP_LTV_HAS_UREF) && !uref))
         return ltv_fail(RQP_ERR_ARG, "rqp_ltv_vectors: a flag names an input whose pointer is NULL");
@@ -1171,8 +1173,12 @@ int rqp_ltv_adjoint_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes) {
 int rqp_ltv_condense_adjoint(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io, void* stream) {
     ltv_err.clear();
     if (int rc = ltv_check(dims, "rqp_ltv_condense_adjoint")) return rc;
-    if (!io || !io->Ad || !io->Bd || !io->x0 || !io->Q || !io->R || !io->Qf || !io->workspace || !io->adjoint_workspace)
+    const bool staged = (dims->flags & RQP_LTV_STAGE_WEIGHTS) != 0;
+    if (!io || !io->Ad || !io->Bd || !io->x0 || !io->Q || !io->R || (!io->Qf && !staged) || !io->workspace || !io->adjoint_workspace)
         return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_adjoint: io, Ad, Bd, x0, Q, R, Qf, workspace and adjoint_workspace are required");
+    if (staged && io->dQf)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_adjoint: RQP_LTV_STAGE_WEIGHTS has no Qf, dQf must be NULL (the terminal "
+                                     "block's gradient is dQ[b][horizon - 1])");
     if (((dims->flags & RQP_LTV_HAS_K) && !io->K) || ((dims->flags & RQP_LTV_HAS_XREF) && !io->xref) ||
         ((dims->flags & RQP_LTV_HAS_UREF) && !io->uref))
         return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_adjoint: a flag names an input whose pointer is NULL");

@@ -6,6 +6,9 @@
 //     y = F v + G x0 + f,
 //     H = sym(F' H_sp F),  A = F,  g = F' H_sp (G x0 + f - yref),  l / u = l_add / u_add - (G x0 + f),
 // H_sp = blkdiag(R, Q, ..., R, Qf) (Q, R, Qf symmetric).  All arithmetic is float64; every output is written once, in T.
+// RQP_LTV_STAGE_WEIGHTS: H_sp = blkdiag(R_0, Q_0, ..., R_{N-1}, Q_{N-1}) per instance, Q [B][N][nx][nx], R [B][N][nu][nu], Qf not
+// read (DESIGN.md section 5 "LTV condensing, stage weights").  The weight source is a template parameter (STAGED) of the kernels
+// that read weights: the shared-weight instantiations are the kernels they were.
 //
 // Three kernels:
 //   k_ltv_transition  one workgroup per instance, ONE THREAD PER COLUMN of [F | G | f] (n + nx + 1 chains).  Column j nu + c
@@ -34,10 +37,17 @@ namespace {
 typedef double cd4 __attribute__((ext_vector_type(4)));
 constexpr int LTV_NUP = 8;        // nu padded (register arrays)
 
+// Stage weights are read straight from global memory.  Every lane of the workgroup reads the same entry of the same block, and
+// the kernels never write the weights: through the constant address space such a load is a scalar load (one per wave, SGPR
+// operands of the FMAs), not 64 vector lanes of the same address.
+typedef const __attribute__((address_space(4))) double* ltv_kptr;
+__device__ __forceinline__ ltv_kptr ltv_uniform(const double* p) { return (ltv_kptr)p; }
+
 struct LtvArgs {
     int B, nx, nu, N, n, m, blk, has_c, has_K, lu_batched;
     const void *Ad, *Bd, *c;                 // [B][N][nx][nx], [B][N][nx][nu], [B][N][nx] (T)
-    const double *Q, *R, *Qf, *K;            // [nx][nx], [nu][nu], [nx][nx], [nu][nx] (K NULL: zero)
+    const double *Q, *R, *Qf, *K;            // [nx][nx], [nu][nu], [nx][nx], [nu][nx] (K NULL: zero); STAGED: Q [B][N][nx][nx],
+                                             // R [B][N][nu][nu], Qf not read
     void *H, *A;                             // [B][n][n], [B][m][n] (T)
     double *F, *W, *Gf, *gmap;               // workspace: [B][m][n], [B][m][n], [B][m][nx + 1], [B][n][nx + 1]
     const void *x0, *xref, *uref, *ladd, *uadd;   // [B][nx], [B][N][nx], [B][N][nu], [m] | [B][m]
@@ -47,7 +57,11 @@ struct LtvArgs {
 // ------------------------------------------------------------------------------------------------------------- transition
 // LDS (doubles): Acl [N][NXP][NXP], K [NUP][NXP], R [NUP][NUP], Q [NXP][NXP], Qf [NXP][NXP], all zero-padded (every inner product
 // has compile-time bounds and the padding contributes exact zeros), then the threads' state columns [NXP + NUP][threads].
-template <typename T, int NXP>
+// STAGED: no R, Q, Qf in LDS (all stages of an instance would not fit beside Acl at the limit shape, and a per-stage slot would
+// need a barrier inside the stage loop, after the surplus threads have returned).  Stage k's blocks are read from global memory
+// at wave-uniform addresses instead (ltv_uniform); the inner products keep their compile-time bounds and their order, the
+// padding terms multiply an exact zero as they do in LDS, so repeated shared blocks give the shared kernel's bits.
+template <typename T, int NXP, bool STAGED>
 __global__ void __launch_bounds__(192) k_ltv_transition(LtvArgs a) {
     extern __shared__ double lds[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -64,15 +78,17 @@ __global__ void __launch_bounds__(192) k_ltv_transition(LtvArgs a) {
         const int r = e / NXP, i = e % NXP;
         Ks[e] = (a.has_K && r < nu && i < nx) ? a.K[r * nx + i] : 0.0;
     }
-    for (int e = tid; e < LTV_NUP * LTV_NUP; e += nt) {
-        const int r = e / LTV_NUP, s = e % LTV_NUP;
-        Rs[e] = (r < nu && s < nu) ? a.R[r * nu + s] : 0.0;
-    }
-    for (int e = tid; e < NXP * NXP; e += nt) {
-        const int r = e / NXP, i = e % NXP;
-        const bool in = r < nx && i < nx;
-        Qs[e] = in ? a.Q[r * nx + i] : 0.0;
-        Qfs[e] = in ? a.Qf[r * nx + i] : 0.0;
+    if constexpr (!STAGED) {
+        for (int e = tid; e < LTV_NUP * LTV_NUP; e += nt) {
+            const int r = e / LTV_NUP, s = e % LTV_NUP;
+            Rs[e] = (r < nu && s < nu) ? a.R[r * nu + s] : 0.0;
+        }
+        for (int e = tid; e < NXP * NXP; e += nt) {
+            const int r = e / NXP, i = e % NXP;
+            const bool in = r < nx && i < nx;
+            Qs[e] = in ? a.Q[r * nx + i] : 0.0;
+            Qfs[e] = in ? a.Qf[r * nx + i] : 0.0;
+        }
     }
     __syncthreads();
     for (int e = tid; e < N * NXP * NXP; e += nt) {                      // Acl_k = A_k - B_k K
@@ -94,7 +110,7 @@ __global__ void __launch_bounds__(192) k_ltv_transition(LtvArgs a) {
     // The thread's state lives twice: x, uu in registers (compile-time indices: the operands of the unrolled inner products) and
     // in its own LDS column xl, ul (run-time row index r of the rolled row loops).  Rolled rows keep the kernel at a few dozen
     // VGPRs; fully unrolled, the NXP^2 LDS reads of a stage were scheduled ahead of their use and spilled.
-    double* xl = Qfs + NXP * NXP + tid;                                  // xl[r * nt], r < NXP
+    double* xl = (STAGED ? Rs : Qfs + NXP * NXP) + tid;                  // xl[r * nt], r < NXP
     double* ul = xl + (size_t)NXP * nt;                                  // ul[r * nt], r < NUP
     double x[NXP], uu[LTV_NUP];
 #pragma unroll
@@ -137,29 +153,62 @@ __global__ void __launch_bounds__(192) k_ltv_transition(LtvArgs a) {
         for (int r = 0; r < LTV_NUP; ++r) uu[r] = ul[r * nt];
         const size_t row0 = (size_t)k * blk;
         if (isF) {
-            const double* Qk = (k == N - 1) ? Qfs : Qs;
             size_t o = row0 * n + col;                                   // one running offset: rows are n apart
+            if constexpr (STAGED) {
+                const ltv_kptr Rk = ltv_uniform(a.R + ((size_t)b * N + k) * nu * nu);
+                const ltv_kptr Qk = ltv_uniform(a.Q + ((size_t)b * N + k) * nx * nx);
 #pragma unroll 1
-            for (int r = 0; r < nu; ++r) {
-                double w = 0.0;
+                for (int r = 0; r < nu; ++r) {
+                    double w = 0.0;
 #pragma unroll
-                for (int s = 0; s < LTV_NUP; ++s) w += Rs[r * LTV_NUP + s] * uu[s];
-                const double v = ul[r * nt];
-                Ao[o] = (T)v;
-                Fo[o] = v;
-                Wo[o] = w;
-                o += n;
-            }
+                    for (int s = 0; s < LTV_NUP; ++s) {                  // index clamped into the row, a padding term switched off
+                        const double q = Rk[r * nu + min(s, nu - 1)];
+                        w += (s < nu ? q : 0.0) * uu[s];
+                    }
+                    const double v = ul[r * nt];
+                    Ao[o] = (T)v;
+                    Fo[o] = v;
+                    Wo[o] = w;
+                    o += n;
+                }
 #pragma unroll 1
-            for (int r = 0; r < nx; ++r) {
-                double w = 0.0;
+                for (int r = 0; r < nx; ++r) {
+                    double w = 0.0;
 #pragma unroll
-                for (int i = 0; i < NXP; ++i) w += Qk[r * NXP + i] * x[i];
-                const double v = xl[r * nt];
-                Ao[o] = (T)v;
-                Fo[o] = v;
-                Wo[o] = w;
-                o += n;
+                    for (int i = 0; i < NXP; ++i) {
+                        const double q = Qk[r * nx + min(i, nx - 1)];
+                        w += (i < nx ? q : 0.0) * x[i];
+                    }
+                    const double v = xl[r * nt];
+                    Ao[o] = (T)v;
+                    Fo[o] = v;
+                    Wo[o] = w;
+                    o += n;
+                }
+            } else {
+                const double* Qk = (k == N - 1) ? Qfs : Qs;
+#pragma unroll 1
+                for (int r = 0; r < nu; ++r) {
+                    double w = 0.0;
+#pragma unroll
+                    for (int s = 0; s < LTV_NUP; ++s) w += Rs[r * LTV_NUP + s] * uu[s];
+                    const double v = ul[r * nt];
+                    Ao[o] = (T)v;
+                    Fo[o] = v;
+                    Wo[o] = w;
+                    o += n;
+                }
+#pragma unroll 1
+                for (int r = 0; r < nx; ++r) {
+                    double w = 0.0;
+#pragma unroll
+                    for (int i = 0; i < NXP; ++i) w += Qk[r * NXP + i] * x[i];
+                    const double v = xl[r * nt];
+                    Ao[o] = (T)v;
+                    Fo[o] = v;
+                    Wo[o] = w;
+                    o += n;
+                }
             }
         } else {
             for (int r = 0; r < nu; ++r) Go[(row0 + r) * nxa + (col - n)] = ul[r * nt];
@@ -266,7 +315,7 @@ __global__ void __launch_bounds__(64) k_ltv_hess(LtvArgs a, int RT, int NA, int 
 
 // ---------------------------------------------------------------------------------------------------------------- vectors
 // LDS (doubles): x0 [nx], yref [m], t = H_sp yref [m]
-template <typename T>
+template <typename T, bool STAGED>
 __global__ void __launch_bounds__(256) k_ltv_vectors(LtvArgs a) {
     extern __shared__ double lds[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
@@ -298,9 +347,10 @@ __global__ void __launch_bounds__(256) k_ltv_vectors(LtvArgs a) {
             const int k = row / blk, r = row % blk;
             double t = 0.0;
             if (r < nu) {
-                for (int q = 0; q < nu; ++q) t += a.R[r * nu + q] * yr[k * blk + q];
+                const double* Rk = STAGED ? a.R + ((size_t)b * N + k) * nu * nu : a.R;
+                for (int q = 0; q < nu; ++q) t += Rk[r * nu + q] * yr[k * blk + q];
             } else {
-                const double* Qk = (k == N - 1) ? a.Qf : a.Q;
+                const double* Qk = STAGED ? a.Q + ((size_t)b * N + k) * nx * nx : ((k == N - 1) ? a.Qf : a.Q);
                 for (int q = 0; q < nx; ++q) t += Qk[(r - nu) * nx + q] * yr[k * blk + nu + q];
             }
             ts[row] = t;
@@ -323,8 +373,9 @@ __global__ void __launch_bounds__(256) k_ltv_vectors(LtvArgs a) {
 }
 
 int nxp_of(int nx) { return (nx + 3) / 4 * 4; }
-size_t transition_lds(int N, int nxp, int threads) {
-    return sizeof(double) * ((size_t)N * nxp * nxp + LTV_NUP * nxp + LTV_NUP * LTV_NUP + 2 * nxp * nxp + (size_t)(nxp + LTV_NUP) * threads);
+size_t transition_lds(int N, int nxp, int threads, bool staged) {
+    const size_t weights = staged ? 0 : LTV_NUP * LTV_NUP + 2 * nxp * nxp;
+    return sizeof(double) * ((size_t)N * nxp * nxp + LTV_NUP * nxp + weights + (size_t)(nxp + LTV_NUP) * threads);
 }
 
 LtvArgs base_args(const rqp_ltv_dims* d, void* ws) {
@@ -344,25 +395,25 @@ LtvArgs base_args(const rqp_ltv_dims* d, void* ws) {
     return a;
 }
 
-template <typename T, int NXP>
+template <typename T, int NXP, bool STAGED>
 hipError_t launch_transition(const LtvArgs& a, hipStream_t s) {
     const int threads = (a.n + a.nx + 1 + 63) / 64 * 64;
-    const size_t lds = transition_lds(a.N, NXP, threads);
+    const size_t lds = transition_lds(a.N, NXP, threads, STAGED);
     if (lds > 48 * 1024) {
-        hipError_t e = rqp_raise_lds_limit((const void*)k_ltv_transition<T, NXP>, lds);
+        hipError_t e = rqp_raise_lds_limit((const void*)k_ltv_transition<T, NXP, STAGED>, lds);
         if (e != hipSuccess) return e;
     }
-    k_ltv_transition<T, NXP><<<a.B, threads, lds, s>>>(a);
+    k_ltv_transition<T, NXP, STAGED><<<a.B, threads, lds, s>>>(a);
     return hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool STAGED>
 hipError_t launch_transition_t(const LtvArgs& a, hipStream_t s) {
     switch (nxp_of(a.nx)) {
-        case 4: return launch_transition<T, 4>(a, s);
-        case 8: return launch_transition<T, 8>(a, s);
-        case 12: return launch_transition<T, 12>(a, s);
-        default: return launch_transition<T, 16>(a, s);
+        case 4: return launch_transition<T, 4, STAGED>(a, s);
+        case 8: return launch_transition<T, 8, STAGED>(a, s);
+        case 12: return launch_transition<T, 12, STAGED>(a, s);
+        default: return launch_transition<T, 16, STAGED>(a, s);
     }
 }
 
@@ -372,7 +423,8 @@ const char* rqp_ltv_check_dims(const rqp_ltv_dims* d) {
     if (!d) return "dims is NULL";
     if (d->batch < 1 || d->nx < 1 || d->nu < 1 || d->horizon < 1) return "batch, nx, nu and horizon must be >= 1";
     if (d->dtype != RQP_F32 && d->dtype != RQP_F64) return "dtype must be RQP_F32 or RQP_F64";
-    if (d->flags & ~(RQP_LTV_HAS_K | RQP_LTV_HAS_C | RQP_LTV_HAS_XREF | RQP_LTV_HAS_UREF | RQP_LTV_BOUNDS_BATCHED)) return "unknown flag";
+    if (d->flags & ~(RQP_LTV_HAS_K | RQP_LTV_HAS_C | RQP_LTV_HAS_XREF | RQP_LTV_HAS_UREF | RQP_LTV_BOUNDS_BATCHED | RQP_LTV_STAGE_WEIGHTS))
+        return "unknown flag";
     return nullptr;
 }
 
@@ -397,7 +449,11 @@ hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const 
                                    const double* R, const double* Qf, const double* K, void* H, void* A, void* ws, hipStream_t s) {
     LtvArgs a = base_args(d, ws);
     a.Ad = Ad; a.Bd = Bd; a.c = c; a.Q = Q; a.R = R; a.Qf = Qf; a.K = K; a.H = H; a.A = A;
-    hipError_t e = (d->dtype == RQP_F32) ? launch_transition_t<float>(a, s) : launch_transition_t<double>(a, s);
+    hipError_t e;
+    if (d->flags & RQP_LTV_STAGE_WEIGHTS)
+        e = (d->dtype == RQP_F32) ? launch_transition_t<float, true>(a, s) : launch_transition_t<double, true>(a, s);
+    else
+        e = (d->dtype == RQP_F32) ? launch_transition_t<float, false>(a, s) : launch_transition_t<double, false>(a, s);
     if (e != hipSuccess) return e;
     const int RT = (a.n + 15) / 16;
     const int NA = (a.nx + 1 + 15) / 16;                                 // tiles of [G | f]: 2 when nx = 16
@@ -415,7 +471,12 @@ hipError_t rqp_ltv_launch_vectors(const rqp_ltv_dims* d, const void* x0, const v
     LtvArgs a = base_args(d, const_cast<void*>(ws));
     a.x0 = x0; a.xref = xref; a.uref = uref; a.ladd = l_add; a.uadd = u_add; a.Q = Q; a.R = R; a.Qf = Qf; a.g = g; a.l = l; a.u = u;
     const size_t lds = sizeof(double) * (size_t)(a.nx + 2 * a.m);
-    if (d->dtype == RQP_F32) k_ltv_vectors<float><<<a.B, 256, lds, s>>>(a);
-    else k_ltv_vectors<double><<<a.B, 256, lds, s>>>(a);
+    if (d->flags & RQP_LTV_STAGE_WEIGHTS) {
+        if (d->dtype == RQP_F32) k_ltv_vectors<float, true><<<a.B, 256, lds, s>>>(a);
+        else k_ltv_vectors<double, true><<<a.B, 256, lds, s>>>(a);
+    } else {
+        if (d->dtype == RQP_F32) k_ltv_vectors<float, false><<<a.B, 256, lds, s>>>(a);
+        else k_ltv_vectors<double, false><<<a.B, 256, lds, s>>>(a);
+    }
     return hipGetLastError();
 }

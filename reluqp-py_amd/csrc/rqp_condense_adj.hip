@@ -28,6 +28,10 @@
 //                    X_k (the columns of stages >= k are zero in X_k and are skipped).
 //   k_ltva_wsum1/2   the weight gradients: per-(instance, stage) entries -> 256 partial sums over fixed slices of the batch
 //                    -> one sum in a fixed order, symmetrised.
+//   k_ltva_wstage    RQP_LTV_STAGE_WEIGHTS instead of the two sums: the entries of every (instance, stage), symmetrised, are the
+//                    outputs dR [B][N][nu][nu], dQ [B][N][nx][nx] themselves.
+// With RQP_LTV_STAGE_WEIGHTS, Q and R are [B][N][..][..] and the kernels that read weights (k_ltva_vectors, k_ltva_blocks) index
+// the block of their instance and stage: a template parameter (STAGED), the shared-weight instantiations are what they were.
 #include <algorithm>
 #include <cstring>
 
@@ -42,11 +46,11 @@ constexpr int WSUM_SLICES = 256;   // first stage of the batch sums
 struct LtvAdjArgs {
     int B, nx, nu, N, n, m, blk, has_K, need_fb, need_w, has_T;
     const void *Ad, *Bd, *x0, *xref, *uref;           // forward inputs (T)
-    const double *Q, *R, *Qf, *K;
+    const double *Q, *R, *Qf, *K;                     // STAGED: Q [B][N][nx][nx], R [B][N][nu][nu], Qf not read
     const double *F, *W, *Gf;                         // forward workspace: [B][m][n], [B][m][n], [B][m][nx + 1]
     const void *dH, *dA, *dg, *dl, *du;               // cotangents (T), NULL = zero
     void *dAd, *dBd, *dc, *dx0, *dxref, *duref;       // outputs (T), NULL = not wanted
-    double *dQ, *dR, *dQf;                            // batch sums, NULL = not wanted
+    double *dQ, *dR, *dQf;                            // batch sums, NULL = not wanted; STAGED: dQ, dR shaped like Q, R, no sum
     double *TF, *vec, *wpart, *wsl;                   // adjoint workspace: [B][m][n], [B][4][m], [B][N][wsz], [slices][2][wsz]
 };
 
@@ -54,7 +58,7 @@ enum { V_E = 0, V_SE = 1, V_FG = 2, V_SB = 3 };
 
 // ---------------------------------------------------------------------------------------------------------------- vectors
 // LDS (doubles): x0 [nx], dg [n], e [m], sb [m], partial sums of dx0 [16][16]
-template <typename T>
+template <typename T, bool STAGED>
 __global__ void __launch_bounds__(256) k_ltva_vectors(LtvAdjArgs a) {
     extern __shared__ double lds[];
     const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -107,9 +111,10 @@ __global__ void __launch_bounds__(256) k_ltva_vectors(LtvAdjArgs a) {
         const int k = row / blk, r = row - k * blk;
         double t = 0.0;
         if (r < nu) {
-            for (int q = 0; q < nu; ++q) t += a.R[r * nu + q] * es[k * blk + q];
+            const double* Rk = STAGED ? a.R + ((size_t)b * N + k) * nu * nu : a.R;
+            for (int q = 0; q < nu; ++q) t += Rk[r * nu + q] * es[k * blk + q];
         } else {
-            const double* Qk = (k == N - 1) ? a.Qf : a.Q;
+            const double* Qk = STAGED ? a.Q + ((size_t)b * N + k) * nx * nx : ((k == N - 1) ? a.Qf : a.Q);
             for (int q = 0; q < nx; ++q) t += Qk[(r - nu) * nx + q] * es[k * blk + nu + q];
         }
         vec[V_SE * m + row] = t;
@@ -176,7 +181,7 @@ __global__ void __launch_bounds__(64) k_ltva_seed(LtvAdjArgs a, int RTm, int JP)
 
 // ----------------------------------------------------------------------------------------------------------------- blocks
 // LDS (doubles): T_k [blk][ld], F_k [blk][ld] (ld odd), R [nu][nu], Q_k [nx][nx], (S e)_k, e_k, (F dg)_k [blk] each, dg [n]
-template <typename T>
+template <typename T, bool STAGED>
 __global__ void __launch_bounds__(256) k_ltva_blocks(LtvAdjArgs a, int ld) {
     extern __shared__ double lds[];
     const int b = blockIdx.x / a.N, k = blockIdx.x % a.N, tid = threadIdx.x;
@@ -190,9 +195,10 @@ __global__ void __launch_bounds__(256) k_ltva_blocks(LtvAdjArgs a, int ld) {
     double* ek = Sek + blk;
     double* Fgk = ek + blk;
     double* gbs = Fgk + blk;
-    const double* Qk = (k == a.N - 1) ? a.Qf : a.Q;
+    const double* Qk = STAGED ? a.Q + (size_t)blockIdx.x * nx * nx : ((k == a.N - 1) ? a.Qf : a.Q);   // (blockIdx.x = b N + k)
+    const double* Rk = STAGED ? a.R + (size_t)blockIdx.x * nu * nu : a.R;
     const double* vec = a.vec + (size_t)b * 4 * m;
-    for (int e = tid; e < nu * nu; e += 256) Rs[e] = a.R[e];
+    for (int e = tid; e < nu * nu; e += 256) Rs[e] = Rk[e];
     for (int e = tid; e < nx * nx; e += 256) Qs[e] = Qk[e];
     for (int r = tid; r < blk; r += 256) {
         Sek[r] = vec[V_SE * m + row0 + r];
@@ -388,6 +394,22 @@ __global__ void __launch_bounds__(256) k_ltva_wsum2(LtvAdjArgs a, int slices) {
     }
 }
 
+// Stage weights: one workgroup per (instance, stage), its wpart entries symmetrised into its blocks of dR and dQ.
+__global__ void __launch_bounds__(256) k_ltva_wstage(LtvAdjArgs a) {
+    const int nx = a.nx, nu = a.nu, wsz = nu * nu + nx * nx;
+    const double* wp = a.wpart + (size_t)blockIdx.x * wsz;               // (blockIdx.x = b N + k)
+    if (a.dR)
+        for (int e = threadIdx.x; e < nu * nu; e += 256) {
+            const int r = e / nu, s = e - r * nu;
+            a.dR[(size_t)blockIdx.x * nu * nu + e] = 0.5 * (wp[r * nu + s] + wp[s * nu + r]);
+        }
+    if (a.dQ)
+        for (int e = threadIdx.x; e < nx * nx; e += 256) {
+            const int r = e / nx, s = e - r * nx, o = nu * nu;
+            a.dQ[(size_t)blockIdx.x * nx * nx + e] = 0.5 * (wp[o + r * nx + s] + wp[o + s * nx + r]);
+        }
+}
+
 int nxp_of(int nx) { return (nx + 3) / 4 * 4; }
 
 template <typename T, int NXP>
@@ -402,14 +424,14 @@ hipError_t launch_sweep(const LtvAdjArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-template <typename T>
+template <typename T, bool STAGED>
 hipError_t launch_adjoint_t(LtvAdjArgs& a, hipStream_t s) {
     const int wsz = a.nu * a.nu + a.nx * a.nx;
     const bool sweep = a.dAd || a.dBd || a.dc, weights = a.dQ || a.dR || a.dQf;
     a.need_fb = sweep;
     a.need_w = weights;
     a.has_T = a.dH != nullptr;
-    k_ltva_vectors<T><<<a.B, 256, sizeof(double) * (size_t)(a.nx + a.n + 2 * a.m + 256), s>>>(a);
+    k_ltva_vectors<T, STAGED><<<a.B, 256, sizeof(double) * (size_t)(a.nx + a.n + 2 * a.m + 256), s>>>(a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || (!sweep && !weights)) return e;
     if (a.has_T) {
@@ -420,10 +442,10 @@ hipError_t launch_adjoint_t(LtvAdjArgs& a, hipStream_t s) {
     const int ld = a.n | 1;
     const size_t blds = sizeof(double) * (2 * (size_t)a.blk * ld + wsz + 3 * a.blk + a.n);
     if (blds > 48 * 1024) {
-        e = rqp_raise_lds_limit((const void*)k_ltva_blocks<T>, blds);
+        e = rqp_raise_lds_limit((const void*)k_ltva_blocks<T, STAGED>, blds);
         if (e != hipSuccess) return e;
     }
-    k_ltva_blocks<T><<<(unsigned)((size_t)a.B * a.N), 256, blds, s>>>(a, ld);
+    k_ltva_blocks<T, STAGED><<<(unsigned)((size_t)a.B * a.N), 256, blds, s>>>(a, ld);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (sweep) {
         switch (nxp_of(a.nx)) {
@@ -434,7 +456,10 @@ hipError_t launch_adjoint_t(LtvAdjArgs& a, hipStream_t s) {
         }
         if (e != hipSuccess) return e;
     }
-    if (weights) {
+    if (weights && STAGED) {
+        k_ltva_wstage<<<(unsigned)((size_t)a.B * a.N), 256, 0, s>>>(a);
+        e = hipGetLastError();
+    } else if (weights) {
         const int slices = std::min(a.B, WSUM_SLICES);
         k_ltva_wsum1<<<slices, 256, 0, s>>>(a, slices);
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -475,5 +500,7 @@ hipError_t rqp_ltv_launch_condense_adjoint(const rqp_ltv_dims* d, const rqp_ltv_
     a.vec = a.TF + B * mn;
     a.wpart = a.vec + B * 4 * a.m;
     a.wsl = a.wpart + B * a.N * wsz;
-    return (d->dtype == RQP_F32) ? launch_adjoint_t<float>(a, s) : launch_adjoint_t<double>(a, s);
+    if (d->flags & RQP_LTV_STAGE_WEIGHTS)
+        return (d->dtype == RQP_F32) ? launch_adjoint_t<float, true>(a, s) : launch_adjoint_t<double, true>(a, s);
+    return (d->dtype == RQP_F32) ? launch_adjoint_t<float, false>(a, s) : launch_adjoint_t<double, false>(a, s);
 }

@@ -75,6 +75,7 @@ class SensitivityIO(ctypes.Structure):
 
 LTV_HAS_K, LTV_HAS_C, LTV_HAS_XREF, LTV_HAS_UREF, LTV_BOUNDS_BATCHED = 1, 2, 4, 8, 16     # RQP_LTV_* (rqp_ltv_dims.flags)
 LTV_STAGE_SHARED_E = 32                                                                   # (the rqp_ltv_stage_* calls only)
+LTV_STAGE_WEIGHTS = 128                                                                   # Q, R per (instance, stage); no Qf
 
 
 class LtvDims(ctypes.Structure):

@@ -135,22 +135,40 @@ class ReLUQPLayer(torch.nn.Module):
         return solver, shapes
 
 
+def _ltv_layer_weights(cd, slot, B, device, Q, R, Qf):
+    """The weights of one forward as the C-ABI reads them: (``mpc._LtvWeights``, (Qd, Rd, Qfd)), symmetric float64 device
+    tensors.  Q, R both matrices: the shared weights.  Q or R with a stage axis ([N, ., .] or [B, N, ., .]): stage weights, both
+    expanded to [B, N, ., .] on the device (a shared Q as Q, ..., Q, Qf) and Qfd = None."""
+    if Q.dim() == 2 and R.dim() == 2:
+        f64 = lambda W: (0.5 * (W.detach() + W.detach().transpose(0, 1))).to(device=device, dtype=torch.float64).contiguous()
+        Qd, Rd, Qfd = f64(Q), f64(R), f64(Qf)
+        return mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"]), (Qd, Rd, Qfd)
+    Qd, Rd, _, _ = mpc._LtvStageWeights(cd.nx, cd.nu, cd.horizon, Q.detach(), R.detach(), None if Qf is None else Qf.detach(),
+                                        None).on(device, B)
+    return mpc._LtvStageTensorWeights(Qd, Rd, slot["K"]), (Qd, Rd, None)
+
+
+def _ltv_saved_weights(slot, Qd, Rd, Qfd):
+    return mpc._LtvStageTensorWeights(Qd, Rd, slot["K"]) if Qfd is None else mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+
+
 class LTVCondenseFunction(torch.autograd.Function):
     """``LTVCondenseFunction.apply(condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add)`` -> ``(H, A, g, l, u)``: the
     condensed QPs of a batch of LTV plants (C-ABI rqp_ltv_condense + rqp_ltv_vectors) with their reverse mode (C-ABI
     rqp_ltv_condense_adjoint, DESIGN.md section 5 "LTV condensing, adjoint").  ``condenser`` is an ``mpc.LTVCondenser``; Ad
     [B, N, nx, nx], Bd [B, N, nx, nu], x0 [B, nx] are device tensors of one precision, c [B, N, nx], xref [B, N, nx], uref
     [B, N, nu] may be None, Q, R, Qf are symmetric tensors (their symmetric part is used, their gradients are symmetric),
-    l_add / u_add [m] or [B, m].  Only the gradients that ``needs_input_grad`` names are computed."""
+    l_add / u_add [m] or [B, m].  Only the gradients that ``needs_input_grad`` names are computed.
+    Stage weights: Q and / or R may be [N, ., .] or [B, N, ., .] (Q_k weighs x_{k+1}; a staged Q comes with ``Qf=None``, a shared
+    Q beside a staged R is repeated as Q, ..., Q, Qf); their gradients come back in the input's shape and dtype, summed over
+    the batch only where the input has no batch axis."""
 
     @staticmethod
     def forward(ctx, condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add):
         cd = condenser
         dtype, device, B = Ad.dtype, Ad.device, Ad.shape[0]
         slot = cd.slot(B, device, dtype)
-        f64 = lambda W: (0.5 * (W.detach() + W.detach().transpose(0, 1))).to(device=device, dtype=torch.float64).contiguous()
-        Qd, Rd, Qfd = f64(Q), f64(R), f64(Qf)
-        w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+        w, (Qd, Rd, Qfd) = _ltv_layer_weights(cd, slot, B, device, Q, R, Qf)
         det = lambda t: None if t is None else t.detach().contiguous()
         Ad, Bd, c, x0, xref, uref = (det(t) for t in (Ad, Bd, c, x0, xref, uref))
         slot["stamp"] = ctx.stamp = cd.next_stamp()
@@ -158,7 +176,8 @@ class LTVCondenseFunction(torch.autograd.Function):
         g, l, u = mpc.ltv_vectors_device((cd.nx, cd.nu, cd.horizon, cd.K is not None, c is not None), x0, l_add.detach(),
                                          u_add.detach(), w, slot["ws"], xref=xref, uref=uref)
         ctx.condenser, ctx.slot = cd, slot
-        ctx.meta = (Q.dtype, R.dtype, Qf.dtype, l_add.dim(), u_add.dim(), l_add.dtype, u_add.dtype)
+        ctx.meta = (Q.dtype, R.dtype, None if Qf is None else Qf.dtype, l_add.dim(), u_add.dim(), l_add.dtype, u_add.dtype)
+        ctx.wdims = (Q.dim(), R.dim())
         ctx.save_for_backward(Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd)
         ctx.set_materialize_grads(False)
         return H, A, g, l, u
@@ -169,7 +188,7 @@ class LTVCondenseFunction(torch.autograd.Function):
         overwritten it.  Returns (slot, weights)."""
         Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors[:9]
         slot = ctx.slot
-        w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+        w = _ltv_saved_weights(slot, Qd, Rd, Qfd)
         if slot["stamp"] != ctx.stamp:
             Hs, As = ctx.condenser.recondense_outputs(slot, Ad.shape[0], Ad.device, Ad.dtype)
             mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, H=Hs, A=As)
@@ -183,11 +202,25 @@ class LTVCondenseFunction(torch.autograd.Function):
         Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors[:9]
         names = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
         want = tuple(k for k, nd in zip(names, ctx.needs_input_grad[1:10]) if nd)
+        staged = Qfd is None
+        if staged and "Qf" in want:                                      # (a shared Q beside a staged R: Qf is stage N-1 of Q)
+            want = tuple(k for k in want if k not in ("Q", "Qf")) + ("Q",)
         grads = [None] * ninputs
         if want:
             slot, w = LTVCondenseFunction.restore(ctx)
             out = mpc.condense_ltv_adjoint_device(Ad, Bd, x0, w, slot["ws"], slot["adj"], xref=xref, uref=uref, dH=gH, dA=gA,
                                                   dg=gg, dl=gl, du=gu, want=want)
+            if staged:                                                   # [B, N, ., .] back to the shape the weight was given in
+                N = Ad.shape[1]
+                if "Q" in out and ctx.wdims[0] == 2:
+                    out["Qf"] = out["Q"][:, N - 1].sum(0)
+                    out["Q"] = out["Q"][:, :N - 1].sum((0, 1))
+                for k, dim in zip(("Q", "R"), ctx.wdims):
+                    if k in out and dim == 3:
+                        out[k] = out[k].sum(0)
+                    elif k in out and dim == 2 and k == "R":
+                        out[k] = out[k].sum((0, 1))
+                out = {k: t for k, t in out.items() if ctx.needs_input_grad[1 + names.index(k)]}
             qdt = dict(Q=ctx.meta[0], R=ctx.meta[1], Qf=ctx.meta[2])
             for i, k in enumerate(names):
                 if k in out:
@@ -218,9 +251,7 @@ class StageConstraintFunction(torch.autograd.Function):
         cd = condenser
         dtype, device, B = Ad.dtype, Ad.device, Ad.shape[0]
         slot = cd.slot(B, device, dtype)
-        f64 = lambda W: (0.5 * (W.detach() + W.detach().transpose(0, 1))).to(device=device, dtype=torch.float64).contiguous()
-        Qd, Rd, Qfd = f64(Q), f64(R), f64(Qf)
-        w = mpc._LtvTensorWeights(Qd, Rd, Qfd, slot["K"])
+        w, (Qd, Rd, Qfd) = _ltv_layer_weights(cd, slot, B, device, Q, R, Qf)
         det = lambda t: None if t is None else t.detach().contiguous()
         Ad, Bd, c, x0, xref, uref = (det(t) for t in (Ad, Bd, c, x0, xref, uref))
         Ed = E.detach().to(device=device, dtype=dtype).contiguous()
@@ -235,7 +266,8 @@ class StageConstraintFunction(torch.autograd.Function):
         A_c = mpc.stage_rows_device(dims4, Ed, slot["ws"])
         l_c, u_c = mpc.stage_vectors_device(dims4, Ed, x0, lo.detach(), hi.detach(), slot["ws"])
         ctx.condenser, ctx.slot, ctx.dims4 = cd, slot, dims4
-        ctx.meta = (Q.dtype, R.dtype, Qf.dtype, E.dim(), lo.dim(), hi.dim(), E.dtype, lo.dtype, hi.dtype)
+        ctx.meta = (Q.dtype, R.dtype, None if Qf is None else Qf.dtype, E.dim(), lo.dim(), hi.dim(), E.dtype, lo.dtype, hi.dtype)
+        ctx.wdims = (Q.dim(), R.dim())
         ctx.save_for_backward(Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd, Ed)
         ctx.set_materialize_grads(False)
         return H, A_c, g, l_c, u_c
@@ -267,6 +299,10 @@ class LTVMPCLayer(torch.nn.Module):
     polish=True``), and the first input is u0 = v[:, :nu] - x0 K' [B, nu]; v [B, n] is the whole QP solution.  Gradients flow to
     Ad, Bd, c, x0, xref, uref and to the weights Q, R, Qf (shared by the batch: summed over it).  The box |u| <= u_max,
     |x| <= x_max and the gain K are constants of the layer.
+
+    Stage weights: Q may be [N, nx, nx] or [B, N, nx, nx] (Q_k weighs x_{k+1}, Q[..., N-1, :, :] is the terminal weight; pass
+    ``Qf=None``) and R [N, nu, nu] or [B, N, nu, nu]; one of them may stay a shared matrix.  Their gradients have the input's
+    shape: per instance and stage for [B, N, ., .], summed over the batch for [N, ., .].
 
     ``LTVMPCLayer(nx, nu, horizon, K=None, stage_rows=nc)`` (no u_max, x_max) replaces the box by nc rows per stage, lo_k <=
     E_k [u_k ; x_{k+1}] <= hi_k, given with every call: ``layer(Ad, Bd, x0, Q, R, Qf, ..., E=, lo=, hi=)`` with E [B, N, nc,
@@ -313,7 +349,8 @@ class LTVMPCLayer(torch.nn.Module):
 
     def _check(self, Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(None, None, None)):
         nx, nu, N = self.nx, self.nu, self.horizon
-        for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("Q", Q), ("R", R), ("Qf", Qf)):
+        staged = torch.is_tensor(Q) and torch.is_tensor(R) and (Q.dim() > 2 or R.dim() > 2)
+        for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("Q", Q), ("R", R)) + (() if staged and Qf is None else (("Qf", Qf),)):
             if not torch.is_tensor(t):
                 raise ValueError("%s must be a torch tensor" % name)
         B, Ns, nxs, nus = mpc._ltv_shapes(Ad, Bd)
@@ -322,12 +359,15 @@ class LTVMPCLayer(torch.nn.Module):
         for name, t, shape in (("x0", x0, (B, nx)), ("c", c, (B, N, nx)), ("xref", xref, (B, N, nx)), ("uref", uref, (B, N, nu))):
             if t is not None and tuple(t.shape) != shape:
                 raise ValueError("%s has shape %s, expected %s" % (name, tuple(t.shape), shape))
-        if tuple(Q.shape) != (nx, nx) or tuple(Qf.shape) != (nx, nx) or tuple(R.shape) != (nu, nu):
+        if staged:                                                       # [N, ., .] or [B, N, ., .]; a staged Q has no Qf
+            mpc._ltv_stage_shapes(nx, nu, N, Q, R, Qf, B=B)
+        elif tuple(Q.shape) != (nx, nx) or tuple(Qf.shape) != (nx, nx) or tuple(R.shape) != (nu, nu):
             raise ValueError("Q, Qf must be [%d, %d] and R [%d, %d]" % (nx, nx, nu, nu))
         # symmetric up to rounding, as BatchedLTVMPC asks (the symmetric part is what is used); the three tests share one read-back
-        asym = torch.stack([(W.detach() - W.detach().transpose(0, 1)).abs().max() - 1e-9 * W.detach().abs().max()
-                            for W in (Q, R, Qf)]).tolist()
-        for name, a in zip(("Q", "R", "Qf"), asym):
+        sym = [(name, W) for name, W in (("Q", Q), ("R", R), ("Qf", Qf)) if W is not None]
+        asym = torch.stack([(W.detach() - W.detach().transpose(-1, -2)).abs().max() - 1e-9 * W.detach().abs().max()
+                            for _, W in sym]).tolist()
+        for (name, _), a in zip(sym, asym):
             if a > 0:
                 raise ValueError("%s must be symmetric" % name)
         if Ad.dtype not in (torch.float32, torch.float64) or any(t is not None and t.dtype != Ad.dtype for t in (Bd, x0, c, xref, uref)):

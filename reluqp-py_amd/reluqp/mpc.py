@@ -362,23 +362,78 @@ def _ltv_weights(nx, nu, Q, R, Qf, K):
     return Q, R, Qf, K
 
 
-def condense_ltv(Ad, Bd, Q, R, Qf, K=None, c=None):
+# Stage weights: instead of one (Q, R, Qf), R_k weighs u_k and Q_k weighs x_{k+1} (so Q_{N-1} is the terminal weight),
+# H_sp = blkdiag(R_0, Q_0, ..., R_{N-1}, Q_{N-1}), per stage ([N, ., .]) or per instance and stage ([B, N, ., .]).  One of Q, R
+# may stay shared ([., .]): it is repeated, a shared Q as Q, ..., Q, Qf.  A staged Q has no Qf.
+
+def _ltv_staged(Q, R):
+    """True when Q or R carries a stage axis (3-D or 4-D); both plain matrices: the shared-weight path."""
+    return np.ndim(Q) > 2 or np.ndim(R) > 2
+
+
+def _ltv_stage_shapes(nx, nu, N, Q, R, Qf, B=None):
+    """Shape rules of staged weights (numpy arrays or tensors; nothing is read).  ``B``: the batch of the stages, None for one
+    instance (no batch axis allowed).  Returns the batch size the weights themselves name (None: none of them has a batch axis)."""
+    batch = None
+    for name, W, d in (("Q", Q, nx), ("R", R, nu)):
+        shape = tuple(W.shape)
+        ok = (shape == (d, d) or shape == (N, d, d) or (len(shape) == 4 and shape[1:] == (N, d, d)))
+        if not ok:
+            raise ValueError("%s has shape %s, expected %s, %s or %s" % (name, shape, ("B", N, d, d), (N, d, d), (d, d)))
+        if len(shape) == 4:
+            if B is None:
+                raise ValueError("%s has a batch axis %s but the stages have none" % (name, shape))
+            if shape[0] != B or (batch is not None and batch != shape[0]):
+                raise ValueError("%s is for a batch of %d, the stages for %d" % (name, shape[0], B))
+            batch = shape[0]
+    if len(Q.shape) > 2:
+        if Qf is not None:
+            raise ValueError("staged Q has no Qf (Q[..., N-1, :, :] is the terminal weight): Qf must be None")
+    elif Qf is None or tuple(Qf.shape) != (nx, nx):
+        raise ValueError("a shared Q needs Qf [%d, %d] (it is repeated as Q, ..., Q, Qf)" % (nx, nx))
+    return batch
+
+
+def _ltv_stage_expand(N, Q, R, Qf):
+    """numpy: Q, R with a stage axis each ([N, ., .] or [B, N, ., .]); a shared one is repeated (Q as Q, ..., Q, Qf)."""
+    if Q.ndim == 2:
+        Q = np.stack([Q] * (N - 1) + [np.asarray(Qf).astype(Q.dtype)])
+    if R.ndim == 2:
+        R = np.stack([R] * N)
+    return Q, R
+
+
+def condense_ltv(Ad, Bd, Q, R, Qf=None, K=None, c=None):
     """Condensed QP maps of LTV plants on the host (numpy, the formulas as written above).
 
     Ad [N, nx, nx], Bd [N, nx, nu], c [N, nx] (optional) for one instance, or with a leading batch axis.  Returns a dict of
     F [m, n], G [m, nx], f [m], H = sym(F'H_sp F) [n, n], A = F, g_x0 = F'H_sp G [n, nx], g_f = F'H_sp f [n], H_sp [m, m]
     (each with the batch axis when the input has one; H_sp is shared).  Then for an initial state x0 and references:
-    g = g_x0 x0 + g_f - F'H_sp yref, l / u = l_add / u_add - (G x0 + f)  (``ltv_vectors``)."""
+    g = g_x0 x0 + g_f - F'H_sp yref, l / u = l_add / u_add - (G x0 + f)  (``ltv_vectors``).
+
+    Stage weights: Q [N, nx, nx] and / or R [N, nu, nu], or [B, N, ., .] when the stages have a batch axis; Q_k weighs x_{k+1}, a
+    staged Q has no Qf (``Qf=None``, else ValueError); one of Q, R may stay a shared matrix and is repeated (Q as Q, ..., Q,
+    Qf).  H_sp then is per instance when a weight is."""
     Ad, Bd = np.asarray(Ad), np.asarray(Bd)
+    Q, R = np.asarray(Q), np.asarray(R)
+    Qf = None if Qf is None else np.asarray(Qf)
+    if _ltv_staged(Q, R):
+        B, N, nx, nu = (Ad.shape[0] if Ad.ndim == 4 else None,) + tuple(Ad.shape[-3:-1]) + (Bd.shape[-1],)
+        _ltv_stage_shapes(nx, nu, N, Q, R, Qf, B=B)
+    elif Qf is None:
+        raise ValueError("shared weights need Qf")
     if Ad.ndim == 4:
-        outs = [condense_ltv(Ad[b], Bd[b], Q, R, Qf, K=K, c=None if c is None else np.asarray(c)[b]) for b in range(Ad.shape[0])]
+        at = lambda W, b: W[b] if W.ndim == 4 else W
+        outs = [condense_ltv(Ad[b], Bd[b], at(Q, b), at(R, b), Qf, K=K, c=None if c is None else np.asarray(c)[b])
+                for b in range(Ad.shape[0])]
         res = {k: np.stack([o[k] for o in outs]) for k in outs[0] if k != "H_sp"}
-        res["H_sp"] = outs[0]["H_sp"]
+        res["H_sp"] = np.stack([o["H_sp"] for o in outs]) if Q.ndim == 4 or R.ndim == 4 else outs[0]["H_sp"]
         return res
     dt = np.result_type(Ad.dtype, np.float64)                  # float64, or wider when the caller passes longdouble
     Ad, Bd = Ad.astype(dt), Bd.astype(dt)
     N, nx, nu = Ad.shape[0], Ad.shape[1], Bd.shape[2]
-    Q, R, Qf = (np.asarray(a).astype(dt) for a in (Q, R, Qf))
+    Q, R = Q.astype(dt), R.astype(dt)
+    Qf = None if Qf is None else Qf.astype(dt)
     K = np.zeros((nu, nx), dtype=dt) if K is None else np.asarray(K).astype(dt)
     c = np.zeros((N, nx), dtype=dt) if c is None else np.asarray(c).astype(dt)
     Acl = [Ad[k] - Bd[k] @ K for k in range(N)]
@@ -410,8 +465,8 @@ def condense_ltv(Ad, Bd, Q, R, Qf, K=None, c=None):
         F[rx], G[rx], f[rx] = xF[k + 1], xG[k + 1], xf[k + 1]
     H_sp = np.zeros((m, m), dtype=dt)
     for k in range(N):
-        H_sp[k * blk:k * blk + nu, k * blk:k * blk + nu] = R
-        H_sp[k * blk + nu:(k + 1) * blk, k * blk + nu:(k + 1) * blk] = Qf if k == N - 1 else Q
+        H_sp[k * blk:k * blk + nu, k * blk:k * blk + nu] = R[k] if R.ndim == 3 else R
+        H_sp[k * blk + nu:(k + 1) * blk, k * blk + nu:(k + 1) * blk] = Q[k] if Q.ndim == 3 else (Qf if k == N - 1 else Q)
     H = F.T @ H_sp @ F
     H = (H + H.T) / 2
     return dict(F=F, G=G, f=f, H=H, A=F, g_x0=F.T @ H_sp @ G, g_f=F.T @ H_sp @ f, H_sp=H_sp)
@@ -422,7 +477,7 @@ def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None):
     F, G, f = cond["F"], cond["G"], cond["f"]
     x0 = np.asarray(x0, dtype=F.dtype)
     if F.ndim == 3:
-        outs = [ltv_vectors({k: (v if k == "H_sp" else v[b]) for k, v in cond.items()}, x0[b],
+        outs = [ltv_vectors({k: (v if k == "H_sp" and v.ndim == 2 else v[b]) for k, v in cond.items()}, x0[b],
                             np.asarray(l_add)[b] if np.ndim(l_add) == 2 else l_add,
                             np.asarray(u_add)[b] if np.ndim(u_add) == 2 else u_add,
                             None if xref is None else xref[b], None if uref is None else uref[b]) for b in range(F.shape[0])]
@@ -447,7 +502,7 @@ def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None):
 _LTV_VJP_KEYS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf", "l_add", "u_add", "K")
 
 
-def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=None, uref=None,
+def condense_ltv_vjp(Ad, Bd, Q, R, Qf=None, x0=None, l_add=None, u_add=None, K=None, c=None, xref=None, uref=None,
                      dH=None, dA=None, dg=None, dl=None, du=None):
     """Reverse of ``condense_ltv`` + ``ltv_vectors`` on the host (numpy): the cotangents dH [n, n], dA [m, n], dg [n],
     dl, du [m] of (H, A, g, l, u) (an absent one is zero) mapped back to the inputs.  One instance, or a leading batch axis
@@ -455,6 +510,9 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=No
     gradients of Ad, Bd, c, x0, xref, uref, l_add, u_add (batched like the inputs; l_add / u_add summed over the batch when
     shared) and of Q, R, Qf, K (summed over the batch; Q, R, Qf symmetric).  K is a reparametrisation -- u_0 = v_0 - K x0 does
     not depend on it in exact arithmetic -- so its entry only states the derivative of the condensing outputs.
+    Stage weights (``condense_ltv``): the gradients of Q, R come back in the shape the weights were given -- per stage the
+    symmetrised diagonal block of Sb, stacked over the batch for [B, N, ., .], summed over it for [N, ., .] -- and a staged Q has
+    no "Qf" entry.
 
     With S = H_sp, Hs = sym(dH), e = G x0 + f - yref, T = F Hs:
         Fb = dA + 2 S T + (S e) dg',  eb = S F dg,  sb = eb - dl - du,  x0b = G'sb,  yrefb = -eb,  [Gb | fb] = sb [x0' | 1],
@@ -463,16 +521,23 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=No
         k = N-1 .. 0:  Aclb = Lam X_k',  Adb_k = Aclb,  Bdb_k = Lam[:, k nu:(k+1) nu] - Aclb K',  cb_k = Lam[:, f],
                        Lam <- Acl_k' Lam - K' Yb[u_k rows] + Yb[x_k rows]   (k >= 1)."""
     Ad, Bd = np.asarray(Ad), np.asarray(Bd)
+    Q, R = np.asarray(Q), np.asarray(R)
     if Ad.ndim == 4:
         B = Ad.shape[0]
         at = lambda a, b: None if a is None else np.asarray(a)[b]
         lu = lambda a, b: np.asarray(a)[b] if np.ndim(a) == 2 else a
-        outs = [condense_ltv_vjp(Ad[b], Bd[b], Q, R, Qf, np.asarray(x0)[b], lu(l_add, b), lu(u_add, b), K=K, c=at(c, b),
-                                 xref=at(xref, b), uref=at(uref, b), dH=at(dH, b), dA=at(dA, b), dg=at(dg, b), dl=at(dl, b),
-                                 du=at(du, b)) for b in range(B)]
+        wt = lambda W, b: W[b] if W.ndim == 4 else W
+        if _ltv_staged(Q, R):
+            _ltv_stage_shapes(Ad.shape[2], Bd.shape[3], Ad.shape[1], Q, R, Qf if Qf is None else np.asarray(Qf), B=B)
+        outs = [condense_ltv_vjp(Ad[b], Bd[b], wt(Q, b), wt(R, b), Qf, np.asarray(x0)[b], lu(l_add, b), lu(u_add, b), K=K,
+                                 c=at(c, b), xref=at(xref, b), uref=at(uref, b), dH=at(dH, b), dA=at(dA, b), dg=at(dg, b),
+                                 dl=at(dl, b), du=at(du, b)) for b in range(B)]
         res = {}
         for k in _LTV_VJP_KEYS:
-            shared = k in ("Q", "R", "Qf", "K") or (k == "l_add" and np.ndim(l_add) == 1) or (k == "u_add" and np.ndim(u_add) == 1)
+            if k not in outs[0]:                               # (staged Q: no Qf)
+                continue
+            shared = ((k == "Q" and Q.ndim < 4) or (k == "R" and R.ndim < 4) or k in ("Qf", "K")
+                      or (k == "l_add" and np.ndim(l_add) == 1) or (k == "u_add" and np.ndim(u_add) == 1))
             st = np.stack([o[k] for o in outs])
             res[k] = st.sum(0) if shared else st
         return res
@@ -484,7 +549,7 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=No
     Kz, x0 = cast(K, (nu, nx)), cast(x0, (nx,))
     xref, uref = cast(xref, (N, nx)), cast(uref, (N, nu))
     Hb, Ab, gb, lb, ub = cast(dH, (n, n)), cast(dA, (m, n)), cast(dg, (n,)), cast(dl, (m,)), cast(du, (m,))
-    cond = condense_ltv(Ad, Bd, np.asarray(Q).astype(dt), np.asarray(R).astype(dt), np.asarray(Qf).astype(dt), K=Kz,
+    cond = condense_ltv(Ad, Bd, Q.astype(dt), R.astype(dt), None if Qf is None else np.asarray(Qf).astype(dt), K=Kz,
                         c=None if c is None else np.asarray(c).astype(dt))
     F, G, f, S = cond["F"], cond["G"], cond["f"], cond["H_sp"]
     e = G @ x0 + f - np.hstack([uref, xref]).reshape(-1)
@@ -496,16 +561,21 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=No
     Yb = np.hstack([Fb, np.outer(sb, x0), sb[:, None]])
     Fg = F @ gb
     Rb, Qb, Qfb = np.zeros((nu, nu), dtype=dt), np.zeros((nx, nx), dtype=dt), np.zeros((nx, nx), dtype=dt)
+    Rst, Qst = np.zeros((N, nu, nu), dtype=dt), np.zeros((N, nx, nx), dtype=dt)
     for k in range(N):                                         # only the diagonal blocks of Sb = F T' + (F dg) e' are needed
         rk = slice(k * blk, (k + 1) * blk)
         Sk = F[rk] @ T[rk].T + np.outer(Fg[rk], e[rk])
         Rb += Sk[:nu, :nu]
         xb = Sk[nu:, nu:]
+        Rst[k], Qst[k] = (Sk[:nu, :nu] + Sk[:nu, :nu].T) / 2, (xb + xb.T) / 2
         if k == N - 1:
             Qfb += xb
         else:
             Qb += xb
     Rb, Qb, Qfb = ((W + W.T) / 2 for W in (Rb, Qb, Qfb))
+    weights = dict(Q=Qst if Q.ndim == 3 else Qb, R=Rst if R.ndim == 3 else Rb)
+    if Q.ndim == 2:
+        weights["Qf"] = Qfb
     Y = np.hstack([F, G, f[:, None]])
     X0 = np.zeros((nx, n + nx + 1), dtype=dt)
     X0[:, n:n + nx] = np.eye(nx, dtype=dt)
@@ -522,8 +592,8 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf, x0, l_add, u_add, K=None, c=None, xref=No
         if k >= 1:
             Lam = (Ad[k] - Bd[k] @ Kz).T @ Lam - Kz.T @ Yu + Yb[(k - 1) * blk + nu:k * blk]
     yr = (-eb).reshape(N, blk)
-    return dict(Ad=Adb, Bd=Bdb, c=cb, x0=G.T @ sb, xref=yr[:, nu:].copy(), uref=yr[:, :nu].copy(), Q=Qb, R=Rb, Qf=Qfb,
-                l_add=lb, u_add=ub, K=Kb)
+    return dict(Ad=Adb, Bd=Bdb, c=cb, x0=G.T @ sb, xref=yr[:, nu:].copy(), uref=yr[:, :nu].copy(), l_add=lb, u_add=ub, K=Kb,
+                **weights)
 
 
 # Stage constraints: instead of the box on y, stage k carries nc rows  lo_k <= E_k [u_k ; x_{k+1}] <= hi_k  (m_c = N nc rows).
@@ -628,6 +698,71 @@ class _LtvTensorWeights(_LtvWeights):
         return self._t
 
 
+class _LtvStageWeights(_LtvWeights):
+    """Stage weights Q [B, N, nx, nx], R [B, N, nu, nu] (and K) as float64 contiguous device tensors, what the C-ABI reads
+    with RQP_LTV_STAGE_WEIGHTS.  Given as numpy arrays or tensors, [B, N, ., .] or [N, ., .]; one of Q, R may be a shared
+    matrix (a shared Q comes with Qf and is repeated as Q, ..., Q, Qf).  The expansion to [B, N, ., .] is done on the device;
+    the symmetric part of every block is used (numpy blocks must be symmetric up to rounding, as the shared weights)."""
+
+    staged = True
+
+    def __init__(self, nx, nu, N, Q, R, Qf, K):
+        arr = lambda W: W if hasattr(W, "detach") or W is None else np.asarray(W, dtype=np.float64)
+        Q, R, Qf = arr(Q), arr(R), arr(Qf)
+        self.batch = _ltv_stage_shapes(nx, nu, N, Q, R, Qf, B=max((W.shape[0] for W in (Q, R) if len(W.shape) == 4), default=None))
+        for name, W in (("Q", Q), ("R", R), ("Qf", Qf)):
+            if isinstance(W, np.ndarray):
+                Wt = np.swapaxes(W, -1, -2)
+                if np.abs(W - Wt).max() > 1e-9 * max(np.abs(W).max(), 1e-300):
+                    raise ValueError("%s must be symmetric (every block)" % name)
+        if K is not None and not hasattr(K, "detach"):
+            K = np.asarray(K, dtype=np.float64)
+        if K is not None and tuple(K.shape) != (nu, nx):
+            raise ValueError("K has shape %s, expected (%d, %d)" % (tuple(K.shape), nu, nx))
+        self.N, self.Q, self.R, self.Qf, self.K = N, Q, R, Qf, K
+        self._dev = {}
+
+    def on(self, device, B):
+        import torch
+        if self.batch is not None and self.batch != B:
+            raise ValueError("the kept stage weights are for a batch of %d, the stages for %d" % (self.batch, B))
+        key = (str(device), B)
+        if key not in self._dev:
+            t = lambda a: None if a is None else torch.as_tensor(a).detach().to(device=device, dtype=torch.float64)
+            Q, R, Qf, K = (t(a) for a in (self.Q, self.R, self.Qf, self.K))
+            if Q.dim() == 2:
+                Q = torch.cat([Q.expand(self.N - 1, -1, -1), Qf.unsqueeze(0)])
+            if R.dim() == 2:
+                R = R.expand(self.N, -1, -1)
+
+            def full(W):                       # [B, N, ., .], the symmetric part of every block
+                W = W if W.dim() == 4 else W.unsqueeze(0).expand(B, -1, -1, -1)
+                return (0.5 * (W + W.transpose(-1, -2))).contiguous()
+
+            self._dev = {key: (full(Q), full(R), None, None if K is None else K.contiguous())}   # (one batch size at a time)
+        return self._dev[key]
+
+
+class _LtvStageTensorWeights(_LtvStageWeights):
+    """Stage weights that already are symmetric float64 contiguous device tensors [B, N, ., .] (the autograd path)."""
+
+    def __init__(self, Q, R, K):
+        self._t = (Q, R, None, K)
+
+    def on(self, device, B):
+        return self._t
+
+
+def _ltv_weights_on(weights, nx, nu, N, B, device):
+    """(Q, R, Qf, K, staged) device tensors of ``weights``: an ``_LtvWeights``, or (Q, R, Qf, K) with shared or staged Q, R."""
+    w = weights
+    if not isinstance(w, _LtvWeights):
+        Q, R, Qf, K = w
+        w = _LtvStageWeights(nx, nu, N, Q, R, Qf, K) if _ltv_staged(Q, R) else _LtvWeights(nx, nu, Q, R, Qf, K)
+    staged = getattr(w, "staged", False)
+    return (w.on(device, B) if staged else w.on(device)) + (staged,)
+
+
 def ltv_adjoint_workspace(batch, nx, nu, horizon, device):
     """The float64 workspace of ``condense_ltv_adjoint_device`` for these sizes (a device tensor)."""
     import ctypes
@@ -646,12 +781,14 @@ LTV_ADJOINT_OUTPUTS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
 
 
 def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspace, xref=None, uref=None, dH=None, dA=None,
-                                dg=None, dl=None, du=None, want=LTV_ADJOINT_OUTPUTS):
+                                dg=None, dl=None, du=None, want=None):
     """Reverse of ``condense_ltv_device`` + ``ltv_vectors_device`` on the device (C-ABI rqp_ltv_condense_adjoint; the host
     statement is ``condense_ltv_vjp``).  ``workspace`` is the forward workspace as ``condense_ltv_device`` left it for these
     Ad, Bd (c); dH [B, n, n], dA [B, m, n], dg [B, n], dl, du [B, m] are the cotangents (None = zero), device tensors of
-    Ad's precision.  ``want`` names the gradients to compute: a dict of those comes back (Ad, Bd, c, x0, xref, uref in Ad's
-    precision; Q, R, Qf float64, summed over the batch).  Enqueued on the current stream."""
+    Ad's precision.  ``want`` names the gradients to compute (None: all): a dict of those comes back (Ad, Bd, c, x0, xref, uref in Ad's
+    precision; Q, R, Qf float64, summed over the batch).  Stage weights (``_LtvStageWeights``, or staged Q, R in the tuple): Q, R
+    come back [B, N, ., .] float64, each block its own instance's and stage's, and "Qf" cannot be wanted.  Enqueued on the
+    current stream."""
     import ctypes
     import torch
     from reluqp import _cabi
@@ -659,13 +796,16 @@ def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspac
     _ltv_check_sizes(nx, nu, N)
     if not torch.is_tensor(Ad) or Ad.device.type != "cuda":
         raise _cabi.RqpUnavailable("condense_ltv_adjoint_device needs device tensors; the host restatement is condense_ltv_vjp")
+    dtype, device = Ad.dtype, Ad.device
+    n, m = N * nu, N * (nx + nu)
+    Q, R, Qf, K, staged = _ltv_weights_on(weights, nx, nu, N, B, device)
+    if want is None:                           # every gradient there is
+        want = tuple(k for k in LTV_ADJOINT_OUTPUTS if not (staged and k == "Qf"))
     unknown = [k for k in want if k not in LTV_ADJOINT_OUTPUTS]
     if unknown:
         raise ValueError("unknown gradient name(s) %s; known: %s" % (unknown, LTV_ADJOINT_OUTPUTS))
-    dtype, device = Ad.dtype, Ad.device
-    n, m = N * nu, N * (nx + nu)
-    w = weights if isinstance(weights, _LtvWeights) else _LtvWeights(nx, nu, *weights)
-    Q, R, Qf, K = w.on(device)
+    if staged and "Qf" in want:
+        raise ValueError("stage weights have no Qf: its gradient is that of Q[:, N-1]")
     opt = lambda t, shape, name: None if t is None else _ltv_in(t, shape, dtype, device, name)
     Ad, Bd, x0 = opt(Ad, (B, N, nx, nx), "Ad"), opt(Bd, (B, N, nx, nu), "Bd"), opt(x0, (B, nx), "x0")
     xref, uref = opt(xref, (B, N, nx), "xref"), opt(uref, (B, N, nu), "uref")
@@ -673,6 +813,8 @@ def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspac
     dl, du = opt(dl, (B, m), "dl"), opt(du, (B, m), "du")
     shapes = dict(Ad=(B, N, nx, nx), Bd=(B, N, nx, nu), c=(B, N, nx), x0=(B, nx), xref=(B, N, nx), uref=(B, N, nu),
                   Q=(nx, nx), R=(nu, nu), Qf=(nx, nx))
+    if staged:
+        shapes.update(Q=(B, N, nx, nx), R=(B, N, nu, nu))
     out = {k: torch.empty(shapes[k], dtype=torch.float64 if k in ("Q", "R", "Qf") else dtype, device=device) for k in want}
     io = _cabi.LtvAdjointIO()
     for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("xref", xref), ("uref", uref), ("Q", Q), ("R", R), ("Qf", Qf), ("K", K),
@@ -682,7 +824,7 @@ def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspac
     for k, t in out.items():
         setattr(io, "d" + k, t.data_ptr())
     flags = ((_cabi.LTV_HAS_K if K is not None else 0) | (_cabi.LTV_HAS_XREF if xref is not None else 0)
-             | (_cabi.LTV_HAS_UREF if uref is not None else 0))
+             | (_cabi.LTV_HAS_UREF if uref is not None else 0) | (_cabi.LTV_STAGE_WEIGHTS if staged else 0))
     dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
                          flags=flags)
     lib = _cabi.load()
@@ -779,8 +921,9 @@ def _ltv_in(t, shape, dtype, device, name):
 def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
     """H [B, n, n], A [B, m, n] of the condensed LTV QPs, built on the device (C-ABI rqp_ltv_condense) from device tensors
     Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]) of the output precision (float32 or float64).  ``weights`` is
-    ``(Q, R, Qf, K)`` (numpy, K may be None) or an ``_LtvWeights``; ``workspace`` from ``ltv_workspace`` carries the maps the
-    vector step needs.  ``H`` / ``A``: optional output tensors.  Enqueued on the current stream; returns (H, A)."""
+    ``(Q, R, Qf, K)`` (numpy, K may be None) or an ``_LtvWeights``; staged Q [B, N, nx, nx] or [N, nx, nx] and / or R in the tuple
+    (then Qf = None for a staged Q), or an ``_LtvStageWeights``, select the stage-weight kernels (RQP_LTV_STAGE_WEIGHTS);
+    ``workspace`` from ``ltv_workspace`` carries the maps the vector step needs.  ``H`` / ``A``: optional output tensors.  Enqueued on the current stream; returns (H, A)."""
     import ctypes
     import torch
     from reluqp import _cabi
@@ -791,13 +934,13 @@ def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
     dtype, device = Ad.dtype, Ad.device
     if dtype not in (torch.float32, torch.float64):
         raise ValueError("Ad must be float32 or float64")
-    w = weights if isinstance(weights, _LtvWeights) else _LtvWeights(nx, nu, *weights)
-    Q, R, Qf, K = w.on(device)
+    Q, R, Qf, K, staged = _ltv_weights_on(weights, nx, nu, N, B, device)
     n, m = N * nu, N * (nx + nu)
     Ad, Bd = _ltv_in(Ad, (B, N, nx, nx), dtype, device, "Ad"), _ltv_in(Bd, (B, N, nx, nu), dtype, device, "Bd")
     c = None if c is None else _ltv_in(c, (B, N, nx), dtype, device, "c")
     H, A = _ltv_out(H, (B, n, n), dtype, device, "H"), _ltv_out(A, (B, m, n), dtype, device, "A")
-    flags = (_cabi.LTV_HAS_K if K is not None else 0) | (_cabi.LTV_HAS_C if c is not None else 0)
+    flags = ((_cabi.LTV_HAS_K if K is not None else 0) | (_cabi.LTV_HAS_C if c is not None else 0)
+             | (_cabi.LTV_STAGE_WEIGHTS if staged else 0))
     dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
                          flags=flags)
     lib = _cabi.load()
@@ -812,7 +955,8 @@ def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
 def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, uref=None, g=None, l=None, u=None):
     """g [B, n], l, u [B, m] from the workspace of the last ``condense_ltv_device`` (C-ABI rqp_ltv_vectors).
     ``dims5`` = (nx, nu, horizon, has_K, has_c) of that call; x0 [B, nx] (xref [B, N, nx], uref [B, N, nu]) device tensors of the
-    output precision, l_add / u_add [m] or [B, m].  Enqueued on the current stream; returns (g, l, u)."""
+    output precision, l_add / u_add [m] or [B, m]; ``weights`` as in that call (stage weights: the same ones, for H_sp yref).
+    Enqueued on the current stream; returns (g, l, u)."""
     import ctypes
     import torch
     from reluqp import _cabi
@@ -827,12 +971,12 @@ def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, u
     batched = torch.as_tensor(l_add).dim() == 2
     l_add = _ltv_in(l_add, (B, m) if batched else (m,), dtype, device, "l_add")
     u_add = _ltv_in(u_add, (B, m) if batched else (m,), dtype, device, "u_add")
-    w = weights if isinstance(weights, _LtvWeights) else _LtvWeights(nx, nu, *weights)
-    Q, R, Qf, _ = w.on(device)
+    Q, R, Qf, _, staged = _ltv_weights_on(weights, nx, nu, N, B, device)
     g, l, u = (_ltv_out(g, (B, n), dtype, device, "g"), _ltv_out(l, (B, m), dtype, device, "l"),
                _ltv_out(u, (B, m), dtype, device, "u"))
     flags = ((_cabi.LTV_HAS_K if has_K else 0) | (_cabi.LTV_HAS_C if has_c else 0) | (_cabi.LTV_HAS_XREF if xref is not None else 0)
-             | (_cabi.LTV_HAS_UREF if uref is not None else 0) | (_cabi.LTV_BOUNDS_BATCHED if batched else 0))
+             | (_cabi.LTV_HAS_UREF if uref is not None else 0) | (_cabi.LTV_BOUNDS_BATCHED if batched else 0)
+             | (_cabi.LTV_STAGE_WEIGHTS if staged else 0))
     dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
                          flags=flags)
     lib = _cabi.load()
@@ -955,7 +1099,12 @@ class BatchedLTVMPC(object):
     ``stage_rows=nc`` replaces the box by nc rows per stage, lo_k <= E_k [u_k ; x_{k+1}] <= hi_k (``stage_constraints``;
     u_max and x_max must then be None): ``linearize(Ad, Bd, c=None, E=None)`` takes E [B, N, nc, nu + nx] or shared [N, nc,
     nu + nx] and ``step(x, ..., lo=None, hi=None)`` the bounds [B, N nc] or [N nc]; each is required on first use and kept
-    until replaced.  The QPs then have ``m = N nc`` rows (A_c = E F is built on the device, rqp_ltv_stage_rows)."""
+    until replaced.  The QPs then have ``m = N nc`` rows (A_c = E F is built on the device, rqp_ltv_stage_rows).
+
+    Stage weights: ``linearize(..., Q=, R=)`` takes Q [B, N, nx, nx] or [N, nx, nx] (Q_k weighs x_{k+1}; Q[..., N-1, :, :] is the
+    terminal weight) and / or R [B, N, nu, nu] or [N, nu, nu], numpy or tensors, kept until replaced like E.  Until one is
+    given the constructor's shared (Q, R, Qf) apply, on the shared-weight kernels; given only one of them, the other repeats
+    the constructor's (Q as Q, ..., Q, Qf)."""
 
     def __init__(self, nx, nu, horizon, Q, R, Qf, u_max=None, x_max=None, K=None, solver=None, stage_rows=None, **solver_kw):
         nx, nu, horizon = int(nx), int(nu), int(horizon)
@@ -972,6 +1121,7 @@ class BatchedLTVMPC(object):
         elif u_max is None or x_max is None:
             raise ValueError("u_max and x_max are required without stage_rows")
         self._E = self._lo = self._hi = None
+        self._Qs = self._Rs = self._stage_weights = None
         self.weights = _LtvWeights(nx, nu, Q, R, Qf, K)
         self.K = self.weights.K
         _, l_add, u_add = box_constraints(nx, nu, horizon, u_max, x_max)
@@ -1021,10 +1171,14 @@ class BatchedLTVMPC(object):
         if self.solver_kw.get("devices"):
             torch.cuda.current_stream(device).synchronize()
 
-    def linearize(self, Ad, Bd, c=None, E=None):
+    def _weights(self):
+        return self.weights if self._stage_weights is None else self._stage_weights
+
+    def linearize(self, Ad, Bd, c=None, E=None, Q=None, R=None):
         """New stage matrices Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]): H and A of every instance are rebuilt on the
         device; the solver is set up on the first ``step`` (it needs g, l, u) and re-factored, state kept, afterwards.
-        With ``stage_rows``: E [B, N, nc, nu + nx] or [N, nc, nu + nx], kept until replaced."""
+        With ``stage_rows``: E [B, N, nc, nu + nx] or [N, nc, nu + nx], kept until replaced.
+        Stage weights Q [B, N, nx, nx] or [N, nx, nx], R [B, N, nu, nu] or [N, nu, nu]: kept until replaced."""
         import torch
         from reluqp import _cabi
         B, N, nx, nu = _ltv_shapes(Ad, Bd)
@@ -1044,12 +1198,23 @@ class BatchedLTVMPC(object):
                     raise ValueError("E has shape %s, expected %s or %s" % (tuple(E.shape), (B, N, nc, blk), (N, nc, blk)))
             elif self._E.dim() == 4 and self._E.shape[0] != B:
                 raise ValueError("the kept E is for a batch of %d, the stages for %d" % (self._E.shape[0], B))
+        if Q is not None or R is not None:
+            for name, W, d in (("Q", Q, nx), ("R", R, nu)):
+                if W is not None and tuple(W.shape) not in ((B, N, d, d), (N, d, d)):
+                    raise ValueError("%s has shape %s, expected %s or %s" % (name, tuple(W.shape), (B, N, d, d), (N, d, d)))
+            Qs, Rs = (self._Qs if Q is None else Q), (self._Rs if R is None else R)
+            w = self.weights                   # a weight never given repeats the constructor's shared one
+            self._stage_weights = _LtvStageWeights(nx, nu, N, w.Q if Qs is None else Qs, w.R if Rs is None else Rs,
+                                                   w.Qf if Qs is None else None, self.K)
+            self._Qs, self._Rs = Qs, Rs
+        if self._stage_weights is not None and self._stage_weights.batch not in (None, B):
+            raise ValueError("the kept stage weights are for a batch of %d, the stages for %d" % (self._stage_weights.batch, B))
         if not torch.cuda.is_available():
             raise _cabi.RqpUnavailable("BatchedLTVMPC needs a HIP device; the MI355X build has no CPU path")
         device, dtype = self._place()
         buf = self._buffers(B, device, dtype)
         to = lambda t: torch.as_tensor(t).to(device=device, dtype=dtype)
-        condense_ltv_device(to(Ad), to(Bd), self.weights, buf["ws"], c=None if c is None else to(c), H=buf["H"],
+        condense_ltv_device(to(Ad), to(Bd), self._weights(), buf["ws"], c=None if c is None else to(c), H=buf["H"],
                             A=buf["A"] if nc is None else buf["A_box"])
         if nc is not None:
             if E is not None:
@@ -1080,7 +1245,7 @@ class BatchedLTVMPC(object):
             if lo is not None or hi is not None:
                 raise ValueError("lo, hi need BatchedLTVMPC(stage_rows=nc)")
             return ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
-                                      buf["u_add"], self.weights, buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"], l=buf["l"],
+                                      buf["u_add"], self._weights(), buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"], l=buf["l"],
                                       u=buf["u"])
         for name, t in (("lo", lo), ("hi", hi)):
             if t is not None:
@@ -1088,7 +1253,7 @@ class BatchedLTVMPC(object):
         if self._lo.dim() != self._hi.dim():
             raise ValueError("lo and hi must both be [B, N nc] or both [N nc]")
         g, _, _ = ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
-                                     buf["u_add"], self.weights, buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"],
+                                     buf["u_add"], self._weights(), buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"],
                                      l=buf["l_box"], u=buf["u_box"])
         l, u = stage_vectors_device((buf["B"], self.nx, self.nu, self.horizon), self._E, x, self._lo, self._hi, buf["ws"],
                                     l_c=buf["l"], u_c=buf["u"])

@@ -10,9 +10,13 @@ over the batch on --workers processes plus the host-to-device copy of (H, A) -- 
 scaled to B.  Stage columns (--stage-rows nc, default 6 -> m_c = 120): rqp_ltv_stage_rows, rqp_ltv_stage_vectors and
 rqp_ltv_stage_adjoint next to `condense`, and update(Hx, Ax) + warm solve() of a BatchedLTVMPC(stage_rows=nc) handle (the input
 box as nu rows of E plus nc - nu random half-planes per stage) next to the same two of the box handle at m = 320.
+Stage-weight columns (--stage-weights): `condense`, `vectors` (with xref: the call that reads the weights) and the adjoint with
+Q [B, N, nx, nx], R [B, N, nu, nu] (RQP_LTV_STAGE_WEIGHTS) next to the shared-weight calls of the same run, the two alternating
+call by call (medians of --reps each), on a workspace of their own.
 Per-kernel times (k_ltv_transition among them): run the same command under `rocprofv3 --kernel-trace --stats`.
 
-    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--out profiles/r8_ltv/ltv_bench.json] [--stage-out profiles/r10_ltv_stage/ltv_stage_bench.json]
+    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--stage-weights] [--out profiles/r8_ltv/ltv_bench.json]
+        [--stage-out profiles/r10_ltv_stage/ltv_stage_bench.json] [--stage-weights-out profiles/r11_ltv_stage_cost/ltv_stage_cost_bench.json]
 """
 import argparse
 import json
@@ -60,6 +64,30 @@ def _timed(torch, fn, reps, warm=3):
     return float(np.median(out[warm:])), float(np.min(out[warm:])), float(np.max(out[warm:]))
 
 
+def _timed_ab(torch, fa, fb, reps, warm=3):
+    """fa and fb alternating call by call: ((median, min, max) of fa, the same of fb), ms."""
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    out = ([], [])
+    for _ in range(warm + reps):
+        for fn, o in zip((fa, fb), out):
+            ev[0].record()
+            fn()
+            ev[1].record()
+            ev[1].synchronize()
+            o.append(ev[0].elapsed_time(ev[1]))
+    return tuple((float(np.median(o[warm:])), float(np.min(o[warm:])), float(np.max(o[warm:]))) for o in out)
+
+
+def _stage_weights(rs, B):
+    """Q [B, N, nx, nx], R [B, N, nu, nu]: symmetric positive definite, different for every (instance, stage)."""
+    def blocks(d, w):
+        M = rs.randn(B, N, d, d)
+        W = 0.05 * M @ np.swapaxes(M, -1, -2)
+        W[..., np.arange(d), np.arange(d)] += 1.0 + rs.rand(B, N, d)
+        return w * (1.0 + 0.3 * np.arange(N))[None, :, None, None] * (1.0 + 0.1 * (np.arange(B) % 16))[:, None, None, None] * W
+    return blocks(NX, 1.0), blocks(NU, 0.1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=4096)
@@ -70,6 +98,9 @@ def main():
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "r8_ltv", "ltv_bench.json"))
     ap.add_argument("--stage-out", default=os.path.join(REPO, "profiles", "r10_ltv_stage", "ltv_stage_bench.json"),
                     help="where the stage columns go, next to the condense / update / solve columns of the same run")
+    ap.add_argument("--stage-weights", action="store_true",
+                    help="add the stage-weight columns: condense, vectors and the adjoint with per-(instance, stage) Q, R")
+    ap.add_argument("--stage-weights-out", default=os.path.join(REPO, "profiles", "r11_ltv_stage_cost", "ltv_stage_cost_bench.json"))
     args = ap.parse_args()
     if not NU <= args.stage_rows <= 32:
         ap.error("--stage-rows must be in [%d, 32]: the input box takes %d rows of E, the kernels hold 32" % (NU, NU))
@@ -119,6 +150,28 @@ def main():
         out["condense_adjoint_ms"], out["condense_adjoint_min_ms"], out["condense_adjoint_max_ms"] = _timed(torch, back, args.reps)
         only_x0 = lambda: mpc.condense_ltv_adjoint_device(Adt, Bdt, xt, ctl.weights, buf["ws"], adj_ws, xref=xr, want=("x0",), **cot)
         out["condense_adjoint_x0_only_ms"], _, _ = _timed(torch, only_x0, args.reps)
+        if args.stage_weights:                 # the same three calls with per-(instance, stage) weights, alternating with the shared ones
+            Qs, Rs = _stage_weights(np.random.RandomState(2), B)
+            sw = mpc._LtvStageWeights(NX, NU, N, Qs, Rs, None, K)
+            sw.on(dev, B)
+            del Qs, Rs
+            ws2 = mpc.ltv_workspace(B, NX, NU, N, dev)
+            H2, A2 = torch.empty_like(buf["H"]), torch.empty_like(buf["A"])
+            g2, l2, u2 = torch.empty_like(buf["g"]), torch.empty_like(buf["l"]), torch.empty_like(buf["u"])
+            d5 = (NX, NU, N, True, False)
+            cond_s = lambda: mpc.condense_ltv_device(Adt, Bdt, sw, ws2, H=H2, A=A2)
+            vec = lambda w, ws, g, l, u: (lambda: mpc.ltv_vectors_device(d5, xt, buf["l_add"], buf["u_add"], w, ws, xref=xr, g=g, l=l, u=u))
+            back_s = lambda: mpc.condense_ltv_adjoint_device(Adt, Bdt, xt, sw, ws2, adj_ws, xref=xr, **cot)
+            cond_s()
+            for name, fa, fb in (("condense", cond, cond_s),
+                                 ("vectors_with_xref", vec(ctl.weights, buf["ws"], buf["g"], buf["l"], buf["u"]), vec(sw, ws2, g2, l2, u2)),
+                                 ("condense_adjoint", back, back_s)):
+                a, b = _timed_ab(torch, fa, fb, args.reps)
+                out["ab_%s_shared_ms" % name], out["ab_%s_shared_min_ms" % name], out["ab_%s_shared_max_ms" % name] = a
+                out["ab_%s_stage_weights_ms" % name], out["ab_%s_stage_weights_min_ms" % name], out["ab_%s_stage_weights_max_ms" % name] = b
+                out["ab_%s_stage_over_shared" % name] = b[0] / a[0]
+            ctl.qp_vectors(xt)                 # (the driver's g, l, u as the columns below expect them)
+            del sw, ws2, H2, A2, g2, l2, u2
         # (a second handle on the same data: the columns above stay those of a handle without the adjoint's workspace)
         sd = reluqpth.ReLU_QP()
         sd.setup(buf["H"], buf["g"], buf["A"], buf["l"], buf["u"], device=dev, precision=prec, eps_abs=1e-3, differentiable=True)
@@ -189,6 +242,11 @@ def main():
     os.makedirs(os.path.dirname(args.stage_out), exist_ok=True)
     with open(args.stage_out, "w") as f:
         json.dump(dict(device=torch.cuda.get_device_name(0), results=stage), f, indent=1)
+    if args.stage_weights:
+        sw = [{k: v for k, v in r.items() if k in keep or k.startswith("ab_")} for r in res]
+        os.makedirs(os.path.dirname(args.stage_weights_out), exist_ok=True)
+        with open(args.stage_weights_out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), results=sw), f, indent=1)
 
 
 if __name__ == "__main__":
