@@ -521,6 +521,44 @@ typedef struct rqp_ltv_stage_adjoint_io {
 } rqp_ltv_stage_adjoint_io;
 int rqp_ltv_stage_adjoint(const rqp_ltv_dims* dims, int device, int32_t nc, const rqp_ltv_stage_adjoint_io* io, void* stream);
 
+/* ---- Input-rate (delta u) cost and bounds of LTV MPC problems (DESIGN.md section 5 "LTV condensing, input rates") ----
+ * The cost of rqp_ltv_condense plus a move-suppression term, and slew-rate rows, both on the plant's input u_k = -K x_k + v_k and
+ * both anchored to the input applied before stage 0, uprev [batch][nu] (dims.dtype):
+ *     J = 1/2 (y - yref)' H_sp (y - yref) + 1/2 sum_k (u_k - u_{k-1})' S_k (u_k - u_{k-1}),    u_{-1} = uprev,
+ *     dlo_k <= u_k - u_{k-1} <= dhi_k     (horizon nu rows).
+ * With F[u_k] the nu rows k (nu + nx) .. of F, dF_k = F[u_k] - F[u_{k-1}] (dF_0 = F[u_0]) and ds_k likewise of s = G x0 + f:
+ *     W_rate = H_sp F, its u rows plus S_k dF_k - S_{k+1} dF_{k+1} (S_N = 0),   H = sym(W_rate' F),   gmap = W_rate' [G | f],
+ *     g = gmap [x0; 1] - F' (H_sp yref),  g[0:nu] -= S_0 uprev   (yref does not enter the rate term; g is rounded once),
+ *     A_r,k = dF_k (exact zeros in the columns >= (k + 1) nu),   l_r,k = dlo_k - ds_k + [k = 0] uprev,   u_r,k likewise with dhi_k.
+ * S is [batch][horizon][nu][nu], DEVICE, double, every block symmetric: read as given, like the stage weights.  dlo, dhi are
+ * [horizon nu], or [batch][horizon nu] with RQP_LTV_BOUNDS_BATCHED (dims.dtype); an infinite entry comes back infinite.
+ * RQP_LTV_STAGE_WEIGHTS and HAS_K / HAS_C / HAS_XREF / HAS_UREF work as in the plain calls; the workspace is that of
+ * rqp_ltv_workspace_bytes, its size unchanged.  The contract of the other rqp_ltv_* calls holds: float64 arithmetic, every output
+ * rounded once, enqueued on `stream` of `device`, no allocation, no host synchronisation, no atomics, a launch chain that depends
+ * on dims and NULL pointers only (capturable in a HIP graph), no scratch, the caller's current device restored,
+ * rqp_last_error(NULL).  Sizes: those of rqp_ltv_condense, else RQP_ERR_UNSUPPORTED.  RQP_ERR_ARG: a required pointer (S and
+ * uprev among them) is NULL.
+ *
+ * A workspace written by rqp_ltv_condense_rate holds W_rate and gmap of the rate problem.  It must be read by
+ * rqp_ltv_vectors_rate, not rqp_ltv_vectors (which would leave S_0 uprev out of g), and it must not be given to
+ * rqp_ltv_condense_adjoint: reverse mode of the rate terms is not implemented.  F and [G | f] in it are those of
+ * rqp_ltv_condense: the rqp_ltv_stage_* calls, rqp_ltv_rate_rows and rqp_ltv_rate_bounds read only them and work on the
+ * workspace of either condense call.  The plain entry points and their launch chains are unchanged.                          */
+int rqp_ltv_condense_rate(const rqp_ltv_dims* dims, int device, const void* Ad, const void* Bd, const void* c,
+                          const double* Q, const double* R, const double* Qf, const double* K, const double* S,
+                          void* H, void* A, void* workspace, void* stream);
+int rqp_ltv_vectors_rate(const rqp_ltv_dims* dims, int device, const void* x0, const void* xref, const void* uref,
+                         const void* l_add, const void* u_add, const double* Q, const double* R, const double* Qf,
+                         const double* S, const void* uprev, const void* workspace, void* g, void* l, void* u, void* stream);
+/* The rate rows.  A_r: horizon nu rows of n entries per instance, l_r / u_r: horizon nu entries per instance (dims.dtype);
+ * instance b starts inst_stride ELEMENTS after instance b - 1, so the rows can land directly in the tail of a
+ * [batch][m0 + horizon nu][n] matrix (inst_stride = (m0 + horizon nu) n, A_r = its address + m0 n elements) and of
+ * [batch][m0 + horizon nu] vectors; nothing between the rows of two instances is written.  inst_stride smaller than one
+ * instance's rows: RQP_ERR_ARG; larger than 640 rows (n or 1 elements each): RQP_ERR_UNSUPPORTED, the QP would exceed m = 640. */
+int rqp_ltv_rate_rows(const rqp_ltv_dims* dims, int device, const void* workspace, void* A_r, int64_t inst_stride, void* stream);
+int rqp_ltv_rate_bounds(const rqp_ltv_dims* dims, int device, const void* x0, const void* uprev, const void* dlo,
+                        const void* dhi, const void* workspace, void* l_r, void* u_r, int64_t inst_stride, void* stream);
+
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);
 

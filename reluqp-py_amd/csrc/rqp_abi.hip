@@ -1237,6 +1237,85 @@ int rqp_ltv_stage_adjoint(const rqp_ltv_dims* dims, int device, int32_t nc, cons
     return RQP_OK;
 }
 
+// Input rates: the dims and flags of the plain calls; sizes checked against the rate kernels' own limits as well.
+static int ltv_rate_check(const rqp_ltv_dims* dims, const char* fn) {
+    if (int rc = ltv_check(dims, fn)) return rc;
+    if (const char* w = rqp_ltv_rate_check_size(dims)) return ltv_fail(RQP_ERR_UNSUPPORTED, std::string(fn) + ": " + w);
+    return RQP_OK;
+}
+// The N nu rows of one instance lie inst_stride elements after those of the one before: at least their own size, and with
+// whatever the caller keeps in front of them no more than m = 640 rows.
+static int ltv_rate_stride(const rqp_ltv_dims* dims, int64_t inst_stride, int64_t row_len, const char* fn) {
+    const int64_t rows = (int64_t)dims->horizon * dims->nu;
+    if (inst_stride < rows * row_len)
+        return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": inst_stride is smaller than the horizon nu rows of one instance");
+    if (inst_stride > 640 * row_len)
+        return ltv_fail(RQP_ERR_UNSUPPORTED, std::string(fn) + ": inst_stride spans more than m = 640 rows per instance");
+    return RQP_OK;
+}
+
+int rqp_ltv_condense_rate(const rqp_ltv_dims* dims, int device, const void* Ad, const void* Bd, const void* c, const double* Q,
+                          const double* R, const double* Qf, const double* K, const double* S, void* H, void* A, void* workspace,
+                          void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_rate_check(dims, "rqp_ltv_condense_rate")) return rc;
+    const bool staged = (dims->flags & RQP_LTV_STAGE_WEIGHTS) != 0;
+    if (!Ad || !Bd || !Q || !R || (!Qf && !staged) || !S || !H || !A || !workspace)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_rate: Ad, Bd, Q, R, Qf, S, H, A and workspace are required");
+    if (((dims->flags & RQP_LTV_HAS_K) && !K) || ((dims->flags & RQP_LTV_HAS_C) && !c))
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_condense_rate: a flag names an input whose pointer is NULL");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_condense_rate")) return rc;
+    hipError_t e = rqp_ltv_launch_condense_rate(dims, Ad, Bd, c, Q, R, Qf, K, S, H, A, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_condense_rate: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+int rqp_ltv_vectors_rate(const rqp_ltv_dims* dims, int device, const void* x0, const void* xref, const void* uref,
+                         const void* l_add, const void* u_add, const double* Q, const double* R, const double* Qf, const double* S,
+                         const void* uprev, const void* workspace, void* g, void* l, void* u, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_rate_check(dims, "rqp_ltv_vectors_rate")) return rc;
+    const bool staged = (dims->flags & RQP_LTV_STAGE_WEIGHTS) != 0;
+    if (!x0 || !l_add || !u_add || !Q || !R || (!Qf && !staged) || !S || !uprev || !workspace || !g || !l || !u)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_vectors_rate: x0, l_add, u_add, Q, R, Qf, S, uprev, workspace, g, l and u are required");
+    if (((dims->flags & RQP_LTV_HAS_XREF) && !xref) || ((dims->flags & RQP_LTV_HAS_UREF) && !uref))
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_vectors_rate: a flag names an input whose pointer is NULL");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_vectors_rate")) return rc;
+    hipError_t e = rqp_ltv_launch_vectors_rate(dims, x0, (dims->flags & RQP_LTV_HAS_XREF) ? xref : nullptr,
+                                               (dims->flags & RQP_LTV_HAS_UREF) ? uref : nullptr, l_add, u_add, Q, R, Qf, S, uprev,
+                                               workspace, g, l, u, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_vectors_rate: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+int rqp_ltv_rate_rows(const rqp_ltv_dims* dims, int device, const void* workspace, void* A_r, int64_t inst_stride, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_rate_check(dims, "rqp_ltv_rate_rows")) return rc;
+    if (int rc = ltv_rate_stride(dims, inst_stride, (int64_t)dims->horizon * dims->nu, "rqp_ltv_rate_rows")) return rc;
+    if (!workspace || !A_r) return ltv_fail(RQP_ERR_ARG, "rqp_ltv_rate_rows: workspace and A_r are required");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_rate_rows")) return rc;
+    hipError_t e = rqp_ltv_launch_rate_rows(dims, workspace, A_r, inst_stride, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_rate_rows: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
+int rqp_ltv_rate_bounds(const rqp_ltv_dims* dims, int device, const void* x0, const void* uprev, const void* dlo, const void* dhi,
+                        const void* workspace, void* l_r, void* u_r, int64_t inst_stride, void* stream) {
+    ltv_err.clear();
+    if (int rc = ltv_rate_check(dims, "rqp_ltv_rate_bounds")) return rc;
+    if (int rc = ltv_rate_stride(dims, inst_stride, 1, "rqp_ltv_rate_bounds")) return rc;
+    if (!x0 || !uprev || !dlo || !dhi || !workspace || !l_r || !u_r)
+        return ltv_fail(RQP_ERR_ARG, "rqp_ltv_rate_bounds: x0, uprev, dlo, dhi, workspace, l_r and u_r are required");
+    LtvDevice on;
+    if (int rc = on.enter(device, "rqp_ltv_rate_bounds")) return rc;
+    hipError_t e = rqp_ltv_launch_rate_bounds(dims, x0, uprev, dlo, dhi, workspace, l_r, u_r, inst_stride, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string("rqp_ltv_rate_bounds: ") + hipGetErrorString(e));
+    return RQP_OK;
+}
+
 const char* rqp_last_error(const rqp_handle* h) { return h ? h->err.c_str() : ltv_err.c_str(); }
 
 const char* rqp_version(void) { return RQP_VERSION; }

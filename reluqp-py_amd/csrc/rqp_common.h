@@ -348,6 +348,19 @@ hipError_t rqp_ltv_launch_vectors(const rqp_ltv_dims* d, const void* x0, const v
                                   void* l, void* u, hipStream_t s);
 // where F [B][m][n] and [G | f] [B][m][nx + 1] sit in the forward workspace (host side; for readers outside rqp_condense.hip)
 void rqp_ltv_ws_maps(const rqp_ltv_dims* d, const void* ws, const double** F, const double** Gf);
+double* rqp_ltv_ws_w(const rqp_ltv_dims* d, void* ws);       // W = H_sp F [B][m][n]
+// input rates (rqp_rate.hip; the two *_rate chains are in rqp_condense.hip)
+const char* rqp_ltv_rate_check_size(const rqp_ltv_dims* d);  // RQP_ERR_UNSUPPORTED
+hipError_t rqp_ltv_launch_condense_rate(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
+                                        const double* R, const double* Qf, const double* K, const double* S, void* H, void* A,
+                                        void* ws, hipStream_t s);
+hipError_t rqp_ltv_launch_vectors_rate(const rqp_ltv_dims* d, const void* x0, const void* xref, const void* uref, const void* l_add,
+                                       const void* u_add, const double* Q, const double* R, const double* Qf, const double* S,
+                                       const void* uprev, const void* ws, void* g, void* l, void* u, hipStream_t s);
+hipError_t rqp_ltv_launch_rate_w(const rqp_ltv_dims* d, const double* S, void* ws, hipStream_t s);
+hipError_t rqp_ltv_launch_rate_rows(const rqp_ltv_dims* d, const void* ws, void* Ar, long long inst_stride, hipStream_t s);
+hipError_t rqp_ltv_launch_rate_bounds(const rqp_ltv_dims* d, const void* x0, const void* uprev, const void* dlo, const void* dhi,
+                                      const void* ws, void* lr, void* ur, long long inst_stride, hipStream_t s);
 // stage constraints on the forward workspace (rqp_stage.hip)
 const char* rqp_ltv_stage_check_size(const rqp_ltv_dims* d, int nc);       // RQP_ERR_UNSUPPORTED
 hipError_t rqp_ltv_launch_stage_rows(const rqp_ltv_dims* d, int nc, const void* E, const void* ws, void* Ac, hipStream_t s);

@@ -27,8 +27,12 @@
 //                     known from (N, nx, nu) alone.
 //   k_ltv_vectors     s = G x0 + f, l / u = l_add / u_add - s, g = (F' H_sp G) x0 + F' H_sp f - F' (H_sp yref): one pass over
 //                     [G | f] (and over F when references are given), no matrix products of the condensing repeated.
+// Input rates (rqp_ltv_condense_rate / rqp_ltv_vectors_rate, DESIGN.md section 5 "LTV condensing, input rates"): k_rate_w
+// (rqp_rate.hip) amends W between the first two kernels; k_ltv_hess<T, true> and k_ltv_vectors<T, STAGED, LtvRateArgs> are for those
+// calls alone, the plain calls launch the kernels they always did.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "rqp_common.h"
 
@@ -244,7 +248,10 @@ __device__ __forceinline__ void ltv_hess_loop(const double* __restrict__ W, int 
     }
 }
 
-template <typename T>
+// LEAD (rqp_ltv_condense_rate): W has been amended by the rate terms (rqp_rate.hip) and its staircase leads F's by one stage:
+// column c of W (stage j = c / nu) is non-zero from the u rows of stage j - 1 on.  The H tiles take klo from F's column block
+// J >= I and stay as they are; the [G | f] tiles take it from W's column block I and start one stage earlier.
+template <typename T, bool LEAD = false>
 __global__ void __launch_bounds__(64) k_ltv_hess(LtvArgs a, int RT, int NA, int nitems) {
 #if defined(__gfx950__)
     const int b = blockIdx.x / nitems, lane = threadIdx.x, i16 = lane & 15, kq = lane >> 4;
@@ -262,7 +269,8 @@ __global__ void __launch_bounds__(64) k_ltv_hess(LtvArgs a, int RT, int NA, int 
     const int ld0 = aug0 ? nxa : n, c0 = min(16 * J0 + i16, ld0 - 1);
     const int ld1 = aug1 ? nxa : n, c1 = min(16 * J1 + i16, ld1 - 1);
     // first row that can be non-zero in either operand: column 16 J of F (and of W) belongs to stage floor(16 J / nu)
-    const int klo = ((16 * (aug0 ? I : J0)) / a.nu) * a.blk & ~3;
+    int klo = ((16 * (aug0 ? I : J0)) / a.nu) * a.blk & ~3;
+    if constexpr (LEAD) klo = aug0 ? (max((16 * I) / a.nu - 1, 0) * a.blk & ~3) : klo;
     cd4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
     if (two) ltv_hess_loop<true>(W, n, cw, P0, ld0, c0, P1, ld1, c1, klo, m, kq, acc0, acc1);
     else ltv_hess_loop<false>(W, n, cw, P0, ld0, c0, P1, ld1, c1, klo, m, kq, acc0, acc1);
@@ -315,8 +323,15 @@ __global__ void __launch_bounds__(64) k_ltv_hess(LtvArgs a, int RT, int NA, int 
 
 // ---------------------------------------------------------------------------------------------------------------- vectors
 // LDS (doubles): x0 [nx], yref [m], t = H_sp yref [m]
-template <typename T, bool STAGED>
-__global__ void __launch_bounds__(256) k_ltv_vectors(LtvArgs a) {
+// ARGS = LtvRateArgs (rqp_ltv_vectors_rate): the workspace holds W_rate and gmap of the rate problem; g[0:nu] -= S_0 uprev
+// before the one rounding (F[u_0] = [I 0] exactly).  The plain calls keep ARGS = LtvArgs: their kernel arguments, and their code.
+struct LtvRateArgs : LtvArgs {
+    const double* S;                         // [B][N][nu][nu]
+    const void* uprev;                       // [B][nu] (T)
+};
+
+template <typename T, bool STAGED, typename ARGS = LtvArgs>
+__global__ void __launch_bounds__(256) k_ltv_vectors(ARGS a) {
     extern __shared__ double lds[];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
     const int nx = a.nx, nu = a.nu, N = a.N, n = a.n, m = a.m, blk = a.blk, nxa = nx + 1;
@@ -367,6 +382,14 @@ __global__ void __launch_bounds__(256) k_ltv_vectors(LtvArgs a) {
             double acc = 0.0;
             for (int row = (col / nu) * blk; row < m; ++row) acc += F[(size_t)row * n + col] * ts[row];   // rows above: zeros of F
             s -= acc;
+        }
+        if constexpr (std::is_same<ARGS, LtvRateArgs>::value) {
+            if (col < nu) {
+                const double* S0 = a.S + (size_t)b * N * nu * nu + (size_t)col * nu;
+                double acc = 0.0;
+                for (int q = 0; q < nu; ++q) acc += S0[q] * (double)((const T*)a.uprev)[(size_t)b * nu + q];
+                s -= acc;
+            }
         }
         ((T*)a.g)[(size_t)b * n + col] = (T)s;
     }
@@ -445,8 +468,12 @@ void rqp_ltv_ws_maps(const rqp_ltv_dims* d, const void* ws, const double** F, co
     *Gf = a.Gf;
 }
 
-hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
-                                   const double* R, const double* Qf, const double* K, void* H, void* A, void* ws, hipStream_t s) {
+double* rqp_ltv_ws_w(const rqp_ltv_dims* d, void* ws) { return base_args(d, ws).W; }
+
+// S != NULL: the rate call (k_rate_w between the two kernels, k_ltv_hess<T, true>); else the plain chain, as it was.
+static hipError_t launch_condense(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
+                                  const double* R, const double* Qf, const double* K, const double* S, void* H, void* A, void* ws,
+                                  hipStream_t s) {
     LtvArgs a = base_args(d, ws);
     a.Ad = Ad; a.Bd = Bd; a.c = c; a.Q = Q; a.R = R; a.Qf = Qf; a.K = K; a.H = H; a.A = A;
     hipError_t e;
@@ -460,8 +487,44 @@ hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const 
     int nitems = 0;
     for (int I = 0; I < RT; ++I) nitems += (NA + RT - I + 1) / 2;
     const unsigned grid = (unsigned)((size_t)a.B * nitems);
+    if (S) {
+        e = rqp_ltv_launch_rate_w(d, S, ws, s);
+        if (e != hipSuccess) return e;
+        if (d->dtype == RQP_F32) k_ltv_hess<float, true><<<grid, 64, 0, s>>>(a, RT, NA, nitems);
+        else k_ltv_hess<double, true><<<grid, 64, 0, s>>>(a, RT, NA, nitems);
+        return hipGetLastError();
+    }
     if (d->dtype == RQP_F32) k_ltv_hess<float><<<grid, 64, 0, s>>>(a, RT, NA, nitems);
     else k_ltv_hess<double><<<grid, 64, 0, s>>>(a, RT, NA, nitems);
+    return hipGetLastError();
+}
+
+hipError_t rqp_ltv_launch_condense(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
+                                   const double* R, const double* Qf, const double* K, void* H, void* A, void* ws, hipStream_t s) {
+    return launch_condense(d, Ad, Bd, c, Q, R, Qf, K, nullptr, H, A, ws, s);
+}
+
+hipError_t rqp_ltv_launch_condense_rate(const rqp_ltv_dims* d, const void* Ad, const void* Bd, const void* c, const double* Q,
+                                        const double* R, const double* Qf, const double* K, const double* S, void* H, void* A,
+                                        void* ws, hipStream_t s) {
+    return launch_condense(d, Ad, Bd, c, Q, R, Qf, K, S, H, A, ws, s);
+}
+
+hipError_t rqp_ltv_launch_vectors_rate(const rqp_ltv_dims* d, const void* x0, const void* xref, const void* uref, const void* l_add,
+                                       const void* u_add, const double* Q, const double* R, const double* Qf, const double* S,
+                                       const void* uprev, const void* ws, void* g, void* l, void* u, hipStream_t s) {
+    LtvRateArgs a;
+    static_cast<LtvArgs&>(a) = base_args(d, const_cast<void*>(ws));
+    a.x0 = x0; a.xref = xref; a.uref = uref; a.ladd = l_add; a.uadd = u_add; a.Q = Q; a.R = R; a.Qf = Qf; a.g = g; a.l = l; a.u = u;
+    a.S = S; a.uprev = uprev;
+    const size_t lds = sizeof(double) * (size_t)(a.nx + 2 * a.m);
+    if (d->flags & RQP_LTV_STAGE_WEIGHTS) {
+        if (d->dtype == RQP_F32) k_ltv_vectors<float, true, LtvRateArgs><<<a.B, 256, lds, s>>>(a);
+        else k_ltv_vectors<double, true, LtvRateArgs><<<a.B, 256, lds, s>>>(a);
+    } else {
+        if (d->dtype == RQP_F32) k_ltv_vectors<float, false, LtvRateArgs><<<a.B, 256, lds, s>>>(a);
+        else k_ltv_vectors<double, false, LtvRateArgs><<<a.B, 256, lds, s>>>(a);
+    }
     return hipGetLastError();
 }
 

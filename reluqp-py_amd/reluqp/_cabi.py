@@ -26,7 +26,8 @@ ABI_SYMBOLS = (
     "rqp_warm_start", "rqp_clear_primal_dual", "rqp_solve", "rqp_iterate", "rqp_compute_residuals",
     "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity",
     "rqp_ltv_workspace_bytes", "rqp_ltv_condense", "rqp_ltv_vectors", "rqp_ltv_adjoint_workspace_bytes",
-    "rqp_ltv_condense_adjoint", "rqp_ltv_stage_rows", "rqp_ltv_stage_vectors", "rqp_ltv_stage_adjoint", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
+    "rqp_ltv_condense_adjoint", "rqp_ltv_stage_rows", "rqp_ltv_stage_vectors", "rqp_ltv_stage_adjoint",
+    "rqp_ltv_condense_rate", "rqp_ltv_vectors_rate", "rqp_ltv_rate_rows", "rqp_ltv_rate_bounds", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
     "rqp_last_error", "rqp_version",
 )
 
@@ -158,6 +159,10 @@ def load():
         "rqp_ltv_stage_rows": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, i32] + [vp] * 4),
         "rqp_ltv_stage_vectors": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, i32] + [vp] * 8),
         "rqp_ltv_stage_adjoint": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, i32, ctypes.POINTER(LtvStageAdjointIO), vp]),
+        "rqp_ltv_condense_rate": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 12),
+        "rqp_ltv_vectors_rate": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 15),
+        "rqp_ltv_rate_rows": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, vp, vp, ctypes.c_int64, vp]),
+        "rqp_ltv_rate_bounds": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 7 + [ctypes.c_int64, vp]),
         "rqp_kernel_name": (ctypes.c_char_p, [H]),
         "rqp_destroy": (ctypes.c_int, [H]),
         "rqp_strerror": (ctypes.c_char_p, [ctypes.c_int]),

@@ -403,7 +403,26 @@ def _ltv_stage_expand(N, Q, R, Qf):
     return Q, R
 
 
-def condense_ltv(Ad, Bd, Q, R, Qf=None, K=None, c=None):
+def _rate_difference(N, nx, nu, dt):
+    """D [N nu, m]: (D y)_k = u_k - u_{k-1} on y = [u_0, x_1, ..., u_{N-1}, x_N] (block row 0 picks u_0: u_{-1} is not in y)."""
+    blk = nu + nx
+    D = np.zeros((N * nu, N * blk), dtype=dt)
+    for k in range(N):
+        D[k * nu:(k + 1) * nu, k * blk:k * blk + nu] = np.eye(nu, dtype=dt)
+        if k >= 1:
+            D[k * nu:(k + 1) * nu, (k - 1) * blk:(k - 1) * blk + nu] = -np.eye(nu, dtype=dt)
+    return D
+
+
+def _rate_weight_shapes(nu, N, S, B=None):
+    shape = tuple(S.shape)
+    if not (shape == (nu, nu) or shape == (N, nu, nu) or (len(shape) == 4 and shape[1:] == (N, nu, nu))):
+        raise ValueError("S has shape %s, expected %s, %s or %s" % (shape, ("B", N, nu, nu), (N, nu, nu), (nu, nu)))
+    if len(shape) == 4 and shape[0] != B:
+        raise ValueError("S has a batch axis %s, the stages %s" % (shape, "none" if B is None else "a batch of %d" % B))
+
+
+def condense_ltv(Ad, Bd, Q, R, Qf=None, K=None, c=None, S=None):
     """Condensed QP maps of LTV plants on the host (numpy, the formulas as written above).
 
     Ad [N, nx, nx], Bd [N, nx, nu], c [N, nx] (optional) for one instance, or with a leading batch axis.  Returns a dict of
@@ -413,10 +432,19 @@ def condense_ltv(Ad, Bd, Q, R, Qf=None, K=None, c=None):
 
     Stage weights: Q [N, nx, nx] and / or R [N, nu, nu], or [B, N, ., .] when the stages have a batch axis; Q_k weighs x_{k+1}, a
     staged Q has no Qf (``Qf=None``, else ValueError); one of Q, R may stay a shared matrix and is repeated (Q as Q, ..., Q,
-    Qf).  H_sp then is per instance when a weight is."""
+    Qf).  H_sp then is per instance when a weight is.
+
+    Input rates (section "LTV condensing, input rates"): S [nu, nu], [N, nu, nu] or [B, N, nu, nu] (symmetric blocks) adds
+    1/2 sum_k (u_k - u_{k-1})' S_k (u_k - u_{k-1}), u_{-1} = uprev, to the cost.  With D y the stacked differences and
+    H_rate = D' blkdiag(S_k) D (both formed densely, both returned): H = sym(F'(H_sp + H_rate) F), g_x0 = F'(H_sp + H_rate) G,
+    g_f = F'(H_sp + H_rate) f; H_sp stays the stage cost alone (yref does not enter the rate term), and ``ltv_vectors`` then
+    needs ``uprev``."""
     Ad, Bd = np.asarray(Ad), np.asarray(Bd)
     Q, R = np.asarray(Q), np.asarray(R)
     Qf = None if Qf is None else np.asarray(Qf)
+    S = None if S is None else np.asarray(S)
+    if S is not None:
+        _rate_weight_shapes(Bd.shape[-1], Ad.shape[-3], S, B=Ad.shape[0] if Ad.ndim == 4 else None)
     if _ltv_staged(Q, R):
         B, N, nx, nu = (Ad.shape[0] if Ad.ndim == 4 else None,) + tuple(Ad.shape[-3:-1]) + (Bd.shape[-1],)
         _ltv_stage_shapes(nx, nu, N, Q, R, Qf, B=B)
@@ -424,8 +452,8 @@ def condense_ltv(Ad, Bd, Q, R, Qf=None, K=None, c=None):
         raise ValueError("shared weights need Qf")
     if Ad.ndim == 4:
         at = lambda W, b: W[b] if W.ndim == 4 else W
-        outs = [condense_ltv(Ad[b], Bd[b], at(Q, b), at(R, b), Qf, K=K, c=None if c is None else np.asarray(c)[b])
-                for b in range(Ad.shape[0])]
+        outs = [condense_ltv(Ad[b], Bd[b], at(Q, b), at(R, b), Qf, K=K, c=None if c is None else np.asarray(c)[b],
+                             S=None if S is None else at(S, b)) for b in range(Ad.shape[0])]
         res = {k: np.stack([o[k] for o in outs]) for k in outs[0] if k != "H_sp"}
         res["H_sp"] = np.stack([o["H_sp"] for o in outs]) if Q.ndim == 4 or R.ndim == 4 else outs[0]["H_sp"]
         return res
@@ -467,24 +495,53 @@ def condense_ltv(Ad, Bd, Q, R, Qf=None, K=None, c=None):
     for k in range(N):
         H_sp[k * blk:k * blk + nu, k * blk:k * blk + nu] = R[k] if R.ndim == 3 else R
         H_sp[k * blk + nu:(k + 1) * blk, k * blk + nu:(k + 1) * blk] = Q[k] if Q.ndim == 3 else (Qf if k == N - 1 else Q)
-    H = F.T @ H_sp @ F
+    if S is None:
+        H = F.T @ H_sp @ F
+        H = (H + H.T) / 2
+        return dict(F=F, G=G, f=f, H=H, A=F, g_x0=F.T @ H_sp @ G, g_f=F.T @ H_sp @ f, H_sp=H_sp)
+    S = S.astype(dt)
+    S = np.stack([S] * N) if S.ndim == 2 else S
+    D = _rate_difference(N, nx, nu, dt)
+    H_rate = D.T @ _blkdiag_dense(S) @ D
+    FtH = F.T @ (H_sp + H_rate)                                # (formed once: the products associate as in the lines above)
+    H = FtH @ F
     H = (H + H.T) / 2
-    return dict(F=F, G=G, f=f, H=H, A=F, g_x0=F.T @ H_sp @ G, g_f=F.T @ H_sp @ f, H_sp=H_sp)
+    return dict(F=F, G=G, f=f, H=H, A=F, g_x0=FtH @ G, g_f=FtH @ f, H_sp=H_sp, H_rate=H_rate, S=S)
 
 
-def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None):
-    """(g, l, u) of the condensed LTV QP from ``condense_ltv``'s maps (one instance: x0 [nx]; batch: x0 [B, nx])."""
+def _blkdiag_dense(blocks):
+    """blkdiag of [N, d, d] blocks, written out in the blocks' dtype."""
+    N, d = blocks.shape[0], blocks.shape[1]
+    M = np.zeros((N * d, N * d), dtype=blocks.dtype)
+    for k in range(N):
+        M[k * d:(k + 1) * d, k * d:(k + 1) * d] = blocks[k]
+    return M
+
+
+def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None, uprev=None):
+    """(g, l, u) of the condensed LTV QP from ``condense_ltv``'s maps (one instance: x0 [nx]; batch: x0 [B, nx]).
+    Maps condensed with a rate weight S need ``uprev`` [nu] ([B, nu]), the input applied before stage 0:
+    g -= F' D' blkdiag(S_k) [uprev; 0; ...] (= S_0 uprev in the first nu entries, F[u_0] = [I 0])."""
     F, G, f = cond["F"], cond["G"], cond["f"]
     x0 = np.asarray(x0, dtype=F.dtype)
+    if ("S" in cond) != (uprev is not None):
+        raise ValueError("uprev is needed exactly when the maps were condensed with a rate weight S")
     if F.ndim == 3:
         outs = [ltv_vectors({k: (v if k == "H_sp" and v.ndim == 2 else v[b]) for k, v in cond.items()}, x0[b],
                             np.asarray(l_add)[b] if np.ndim(l_add) == 2 else l_add,
                             np.asarray(u_add)[b] if np.ndim(u_add) == 2 else u_add,
-                            None if xref is None else xref[b], None if uref is None else uref[b]) for b in range(F.shape[0])]
+                            None if xref is None else xref[b], None if uref is None else uref[b],
+                            None if uprev is None else np.asarray(uprev)[b]) for b in range(F.shape[0])]
         return tuple(np.stack([o[i] for o in outs]) for i in range(3))
     m, nx = G.shape
     s = G @ x0 + f
     g = cond["g_x0"] @ x0 + cond["g_f"]
+    if uprev is not None:
+        Sk = cond["S"]
+        N, nu = Sk.shape[0], Sk.shape[1]
+        e0 = np.zeros(N * nu, dtype=F.dtype)
+        e0[:nu] = np.asarray(uprev).astype(F.dtype)
+        g = g - F.T @ (_rate_difference(N, nx, nu, F.dtype).T @ (_blkdiag_dense(Sk) @ e0))
     if xref is not None or uref is not None:
         n = F.shape[1]
         # (N, nu) from the shapes: m = N (nu + nx), n = N nu
@@ -497,6 +554,34 @@ def ltv_vectors(cond, x0, l_add, u_add, xref=None, uref=None):
             yref[:, nu:] = xref
         g = g - F.T @ (cond["H_sp"] @ yref.reshape(-1))
     return g, np.asarray(l_add, dtype=F.dtype) - s, np.asarray(u_add, dtype=F.dtype) - s
+
+
+def rate_constraints(cond, x0, uprev, dlo, dhi):
+    """(A_r, l_r, u_r) of the slew-rate rows dlo_k <= u_k - u_{k-1} <= dhi_k, u_{-1} = uprev, on the maps of ``condense_ltv``
+    (numpy, by the definitions: D formed densely).  With y = F v + s:  A_r = D F,  l_r = dlo - D s + [uprev; 0; ...],
+    u_r = dhi - D s + [uprev; 0; ...]  (N nu rows; u_k is the plant's input -K x_k + v_k).  One instance: x0 [nx], uprev [nu],
+    dlo, dhi [N nu]; or ``cond`` with a batch axis, x0 [B, nx], uprev [B, nu], dlo / dhi [B, N nu] or shared [N nu]."""
+    F, G, f = cond["F"], cond["G"], cond["f"]
+    x0, uprev = np.asarray(x0).astype(F.dtype), np.asarray(uprev).astype(F.dtype)
+    if F.ndim == 3:
+        outs = [rate_constraints({k: v[b] for k, v in cond.items() if k in ("F", "G", "f")}, x0[b], uprev[b],
+                                 np.asarray(dlo)[b] if np.ndim(dlo) == 2 else dlo, np.asarray(dhi)[b] if np.ndim(dhi) == 2 else dhi)
+                for b in range(F.shape[0])]
+        return tuple(np.stack([o[i] for o in outs]) for i in range(3))
+    m, nx = G.shape
+    n = F.shape[1]
+    N = (m - n) // nx
+    nu = n // N
+    if uprev.shape != (nu,):
+        raise ValueError("uprev has shape %s, expected (%d,)" % (uprev.shape, nu))
+    dlo, dhi = np.asarray(dlo).astype(F.dtype), np.asarray(dhi).astype(F.dtype)
+    if dlo.shape != (n,) or dhi.shape != (n,):
+        raise ValueError("dlo, dhi have shapes %s, %s, expected (%d,)" % (dlo.shape, dhi.shape, n))
+    D = _rate_difference(N, nx, nu, F.dtype)
+    ds = D @ (G @ x0 + f)
+    e0 = np.zeros(n, dtype=F.dtype)
+    e0[:nu] = uprev
+    return D @ F, dlo - ds + e0, dhi - ds + e0
 
 
 _LTV_VJP_KEYS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf", "l_add", "u_add", "K")
@@ -918,12 +1003,30 @@ def _ltv_in(t, shape, dtype, device, name):
     return t
 
 
-def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
+def rate_weight_device(S, nu, N, B, device):
+    """S [nu, nu], [N, nu, nu] or [B, N, nu, nu] (numpy or tensor) as the C-ABI reads it: a float64 contiguous device tensor
+    [B, N, nu, nu], the symmetric part of every block (numpy blocks must be symmetric up to rounding, like the other weights).
+    The expansion is done on the device."""
+    import torch
+    if not hasattr(S, "detach"):
+        S = np.asarray(S, dtype=np.float64)
+        if S.ndim >= 2 and np.abs(S - np.swapaxes(S, -1, -2)).max() > 1e-9 * max(np.abs(S).max(), 1e-300):
+            raise ValueError("S must be symmetric (every block)")
+    _rate_weight_shapes(nu, N, S, B=B)
+    S = torch.as_tensor(S).detach().to(device=device, dtype=torch.float64)
+    S = S.expand(B, N, nu, nu)
+    return (0.5 * (S + S.transpose(-1, -2))).contiguous()
+
+
+def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None, S=None):
     """H [B, n, n], A [B, m, n] of the condensed LTV QPs, built on the device (C-ABI rqp_ltv_condense) from device tensors
     Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]) of the output precision (float32 or float64).  ``weights`` is
     ``(Q, R, Qf, K)`` (numpy, K may be None) or an ``_LtvWeights``; staged Q [B, N, nx, nx] or [N, nx, nx] and / or R in the tuple
     (then Qf = None for a staged Q), or an ``_LtvStageWeights``, select the stage-weight kernels (RQP_LTV_STAGE_WEIGHTS);
-    ``workspace`` from ``ltv_workspace`` carries the maps the vector step needs.  ``H`` / ``A``: optional output tensors.  Enqueued on the current stream; returns (H, A)."""
+    ``workspace`` from ``ltv_workspace`` carries the maps the vector step needs.  ``H`` / ``A``: optional output tensors.
+    ``S``: a rate weight from ``rate_weight_device`` ([B, N, nu, nu] float64 on the device) adds the input-rate cost
+    (C-ABI rqp_ltv_condense_rate); the workspace then serves ``ltv_vectors_device(..., S=, uprev=)`` only, and no adjoint.
+    Enqueued on the current stream; returns (H, A)."""
     import ctypes
     import torch
     from reluqp import _cabi
@@ -944,6 +1047,15 @@ def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
     dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
                          flags=flags)
     lib = _cabi.load()
+    if S is not None:
+        S = _rate_tensor(S, (B, N, nu, nu), device)
+        with torch.cuda.device(device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _cabi.check(None, lib.rqp_ltv_condense_rate(ctypes.byref(dims), device.index or 0, _cabi.ptr(Ad), _cabi.ptr(Bd),
+                                                        _cabi.ptr(c), _cabi.ptr(Q), _cabi.ptr(R), _cabi.ptr(Qf), _cabi.ptr(K),
+                                                        _cabi.ptr(S), _cabi.ptr(H), _cabi.ptr(A), _cabi.ptr(workspace), stream),
+                        "rqp_ltv_condense_rate", handleless=True)
+        return H, A
     with torch.cuda.device(device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         _cabi.check(None, lib.rqp_ltv_condense(ctypes.byref(dims), device.index or 0, _cabi.ptr(Ad), _cabi.ptr(Bd), _cabi.ptr(c),
@@ -952,15 +1064,27 @@ def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None):
     return H, A
 
 
-def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, uref=None, g=None, l=None, u=None):
+def _rate_tensor(S, shape, device):
+    import torch
+    if (not torch.is_tensor(S) or S.dtype != torch.float64 or S.device != device or tuple(S.shape) != tuple(shape)
+            or not S.is_contiguous()):
+        raise ValueError("S must be a contiguous float64 tensor of shape %s on %s (rate_weight_device)" % (tuple(shape), device))
+    return S
+
+
+def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, uref=None, g=None, l=None, u=None, S=None,
+                       uprev=None):
     """g [B, n], l, u [B, m] from the workspace of the last ``condense_ltv_device`` (C-ABI rqp_ltv_vectors).
     ``dims5`` = (nx, nu, horizon, has_K, has_c) of that call; x0 [B, nx] (xref [B, N, nx], uref [B, N, nu]) device tensors of the
     output precision, l_add / u_add [m] or [B, m]; ``weights`` as in that call (stage weights: the same ones, for H_sp yref).
+    A workspace of ``condense_ltv_device(..., S=)`` needs the same ``S`` and ``uprev`` [B, nu] here (C-ABI rqp_ltv_vectors_rate).
     Enqueued on the current stream; returns (g, l, u)."""
     import ctypes
     import torch
     from reluqp import _cabi
     nx, nu, N, has_K, has_c = dims5
+    if (S is None) != (uprev is None):
+        raise ValueError("S and uprev go together: both for a workspace condensed with a rate weight, else neither")
     if not torch.is_tensor(x0) or x0.device.type != "cuda":
         raise _cabi.RqpUnavailable("ltv_vectors_device needs device tensors; the host restatement is ltv_vectors")
     dtype, device, B = x0.dtype, x0.device, x0.shape[0]
@@ -980,6 +1104,16 @@ def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, u
     dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
                          flags=flags)
     lib = _cabi.load()
+    if S is not None:
+        S, uprev = _rate_tensor(S, (B, N, nu, nu), device), _ltv_in(uprev, (B, nu), dtype, device, "uprev")
+        with torch.cuda.device(device):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+            _cabi.check(None, lib.rqp_ltv_vectors_rate(ctypes.byref(dims), device.index or 0, _cabi.ptr(x0), _cabi.ptr(xref),
+                                                       _cabi.ptr(uref), _cabi.ptr(l_add), _cabi.ptr(u_add), _cabi.ptr(Q), _cabi.ptr(R),
+                                                       _cabi.ptr(Qf), _cabi.ptr(S), _cabi.ptr(uprev), _cabi.ptr(workspace),
+                                                       _cabi.ptr(g), _cabi.ptr(l), _cabi.ptr(u), stream),
+                        "rqp_ltv_vectors_rate", handleless=True)
+        return g, l, u
     with torch.cuda.device(device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
         _cabi.check(None, lib.rqp_ltv_vectors(ctypes.byref(dims), device.index or 0, _cabi.ptr(x0), _cabi.ptr(xref), _cabi.ptr(uref),
@@ -987,6 +1121,88 @@ def ltv_vectors_device(dims5, x0, l_add, u_add, weights, workspace, xref=None, u
                                               _cabi.ptr(workspace), _cabi.ptr(g), _cabi.ptr(l), _cabi.ptr(u), stream),
                     "rqp_ltv_vectors", handleless=True)
     return g, l, u
+
+
+def _rate_call(dims4, dtype, device, what):
+    import torch
+    from reluqp import _cabi
+    B, nx, nu, N = (int(v) for v in dims4)
+    _ltv_check_sizes(nx, nu, N)
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError("dtype must be float32 or float64")
+    if torch.device(device).type != "cuda":
+        raise _cabi.RqpUnavailable("%s needs device tensors; the host restatement is rate_constraints" % what)
+    dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32, flags=0)
+    return _cabi.load(), dims
+
+
+def _rate_tail(t, shape, row0, dtype, device, name):
+    """The tensor the rate rows go into and the element offset of its row ``row0``: ``t`` [B, mt, ...] contiguous with
+    row0 + N nu <= mt, or None: a new one that holds the rate rows alone."""
+    import torch
+    if t is None:
+        if row0:
+            raise ValueError("row0 needs the tensor to write into")
+        return torch.empty(shape, dtype=dtype, device=device)
+    ok = (t.dtype == dtype and t.device == device and t.is_contiguous() and t.dim() == len(shape) and t.shape[0] == shape[0]
+          and tuple(t.shape[2:]) == tuple(shape[2:]) and 0 <= row0 and row0 + shape[1] <= t.shape[1])
+    if not ok:
+        raise ValueError("%s must be a contiguous %s tensor [%d, mt, ...] on %s with room for %d rows from row %d on"
+                         % (name, dtype, shape[0], device, shape[1], row0))
+    return t
+
+
+def rate_rows_device(dims4, workspace, dtype, A_r=None, row0=0):
+    """A_r,k = F[u_k] - F[u_{k-1}] [B, N nu, n] from the workspace of the last ``condense_ltv_device`` (C-ABI rqp_ltv_rate_rows).
+    ``dims4`` = (B, nx, nu, horizon) of that call, ``dtype`` the output precision.  ``A_r``: optional contiguous tensor
+    [B, mt, n] to write into, the rate rows landing in its rows row0 .. row0 + N nu of every instance (the others are not
+    touched).  Enqueued on the current stream; returns the tensor written into (entries right of the staircase: exact zeros)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    device = workspace.device
+    lib, dims = _rate_call(dims4, dtype, device, "rate_rows_device")
+    n = dims.horizon * dims.nu
+    A_r = _rate_tail(A_r, (dims.batch, n, n), row0, dtype, device, "A_r")
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_rate_rows(ctypes.byref(dims), device.index or 0, _cabi.ptr(workspace),
+                                                ctypes.c_void_p(A_r.data_ptr() + row0 * n * A_r.element_size()),
+                                                A_r.shape[1] * n, stream), "rqp_ltv_rate_rows", handleless=True)
+    return A_r
+
+
+def rate_bounds_device(dims4, x0, uprev, dlo, dhi, workspace, l_r=None, u_r=None, row0=0):
+    """l_r,k = dlo_k - ds_k + [k = 0] uprev, u_r likewise with dhi [B, N nu], ds the differences of s = G x0 + f of the
+    workspace over the u rows (C-ABI rqp_ltv_rate_bounds).  x0 [B, nx], uprev [B, nu]; dlo, dhi [N nu] or [B, N nu] (infinite
+    entries stay infinite).  ``l_r`` / ``u_r``: optional contiguous tensors [B, mt] to write into, from entry row0 on.
+    Enqueued on the current stream; returns (l_r, u_r)."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    if not torch.is_tensor(x0):
+        raise ValueError("x0 must be a torch tensor")
+    dtype, device = x0.dtype, x0.device
+    lib, dims = _rate_call(dims4, dtype, device, "rate_bounds_device")
+    B, n = dims.batch, dims.horizon * dims.nu
+    x0, uprev = _ltv_in(x0, (B, dims.nx), dtype, device, "x0"), _ltv_in(uprev, (B, dims.nu), dtype, device, "uprev")
+    batched = torch.as_tensor(dlo).dim() == 2
+    dlo = _ltv_in(dlo, (B, n) if batched else (n,), dtype, device, "dlo")
+    dhi = _ltv_in(dhi, (B, n) if batched else (n,), dtype, device, "dhi")
+    if batched:
+        dims.flags |= _cabi.LTV_BOUNDS_BATCHED
+    if (l_r is None) != (u_r is None):
+        raise ValueError("l_r and u_r go together")
+    l_r, u_r = _rate_tail(l_r, (B, n), row0, dtype, device, "l_r"), _rate_tail(u_r, (B, n), row0, dtype, device, "u_r")
+    if l_r.shape != u_r.shape:
+        raise ValueError("l_r and u_r must have the same shape")
+    at = lambda t: ctypes.c_void_p(t.data_ptr() + row0 * t.element_size())
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _cabi.check(None, lib.rqp_ltv_rate_bounds(ctypes.byref(dims), device.index or 0, _cabi.ptr(x0), _cabi.ptr(uprev),
+                                                  _cabi.ptr(dlo), _cabi.ptr(dhi), _cabi.ptr(workspace), at(l_r), at(u_r),
+                                                  l_r.shape[1], stream), "rqp_ltv_rate_bounds", handleless=True)
+    return l_r, u_r
 
 
 def _stage_call(dims4, E, what):
@@ -1104,9 +1320,19 @@ class BatchedLTVMPC(object):
     Stage weights: ``linearize(..., Q=, R=)`` takes Q [B, N, nx, nx] or [N, nx, nx] (Q_k weighs x_{k+1}; Q[..., N-1, :, :] is the
     terminal weight) and / or R [B, N, nu, nu] or [N, nu, nu], numpy or tensors, kept until replaced like E.  Until one is
     given the constructor's shared (Q, R, Qf) apply, on the shared-weight kernels; given only one of them, the other repeats
-    the constructor's (Q as Q, ..., Q, Qf)."""
+    the constructor's (Q as Q, ..., Q, Qf).
 
-    def __init__(self, nx, nu, horizon, Q, R, Qf, u_max=None, x_max=None, K=None, solver=None, stage_rows=None, **solver_kw):
+    Input rates (``rate_constraints``; both act on the plant's input u_k = -K x_k + v_k and start from the input applied before
+    stage 0): ``rate_weight=S`` [nu, nu] adds the move-suppression cost 1/2 sum_k (u_k - u_{k-1})' S (u_k - u_{k-1});
+    ``linearize(..., S=)`` takes S [B, N, nu, nu], [N, nu, nu] or [nu, nu], kept until replaced.  ``du_max=`` (a scalar or [nu];
+    inf: rows whose bounds come later) appends N nu slew-rate rows |u_k - u_{k-1}| <= du_max after the box or the stage rows,
+    ``m = m0 + N nu``; ``step(x, ..., du_lo=, du_hi=)`` replaces their bounds ([N nu] or [B, N nu], kept until replaced).
+    ``step(..., u_prev=)`` [B, nu] is required on the first step and defaults to the u_0 the previous step returned afterwards.
+    With rate rows the base rows are built in a buffer of their own and copied into the larger A, l, u (one strided copy of
+    B m0 n entries per ``linearize``, of 2 B m0 per step).  Without any rate argument the driver makes the calls it always made."""
+
+    def __init__(self, nx, nu, horizon, Q, R, Qf, u_max=None, x_max=None, K=None, solver=None, stage_rows=None, rate_weight=None,
+                 du_max=None, **solver_kw):
         nx, nu, horizon = int(nx), int(nu), int(horizon)
         _ltv_check_sizes(nx, nu, horizon)
         self.nx, self.nu, self.horizon = nx, nu, horizon
@@ -1122,6 +1348,23 @@ class BatchedLTVMPC(object):
             raise ValueError("u_max and x_max are required without stage_rows")
         self._E = self._lo = self._hi = None
         self._Qs = self._Rs = self._stage_weights = None
+        self._S = self._S_dev = self._uprev = self._du_lo = self._du_hi = None
+        if rate_weight is not None:
+            self._S = np.asarray(rate_weight, dtype=np.float64)
+            if self._S.shape != (nu, nu):
+                raise ValueError("rate_weight has shape %s, expected (%d, %d) (stage-varying S: linearize(S=))" % (self._S.shape, nu, nu))
+            if np.abs(self._S - self._S.T).max() > 1e-9 * max(np.abs(self._S).max(), 1e-300):
+                raise ValueError("rate_weight must be symmetric")
+        self.m_base, self.rate_rows = self.m, du_max is not None
+        if self.rate_rows:
+            du = np.asarray(du_max, dtype=np.float64)
+            if du.shape not in ((), (nu,)) or np.isnan(du).any() or (du < 0).any():
+                raise ValueError("du_max must be a non-negative scalar or [%d]" % nu)
+            self._du = np.tile(np.broadcast_to(du, (nu,)), horizon)
+            self.m = self.m_base + horizon * nu
+            if self.m > LTV_LIMITS["m"]:
+                raise ValueError("unsupported size: %d base rows + %d rate rows = %d, the QPs hold m <= %d"
+                                 % (self.m_base, horizon * nu, self.m, LTV_LIMITS["m"]))
         self.weights = _LtvWeights(nx, nu, Q, R, Qf, K)
         self.K = self.weights.K
         _, l_add, u_add = box_constraints(nx, nu, horizon, u_max, x_max)
@@ -1156,6 +1399,13 @@ class BatchedLTVMPC(object):
                              Kt=None if self.K is None else torch.as_tensor(self.K.T.copy(), dtype=dtype, device=device))
             if self.stage_rows is not None:    # what rqp_ltv_condense / rqp_ltv_vectors write besides H and g: A = F, the box l, u
                 self._buf.update(A_box=e(B, self.m_box, self.n), l_box=e(B, self.m_box), u_box=e(B, self.m_box))
+            if self.rate_rows:                 # the base rows, copied into the head of A, l, u; the rate rows are written in place
+                self._buf.update(A_base=e(B, self.m_base, self.n), l_base=e(B, self.m_base), u_base=e(B, self.m_base),
+                                 du_lo=torch.as_tensor(-self._du, dtype=dtype, device=device),
+                                 du_hi=torch.as_tensor(self._du, dtype=dtype, device=device))
+                self._buf["A_rows"], self._buf["l_rows"], self._buf["u_rows"] = (self._buf[k + "_base"] for k in "Alu")
+            else:
+                self._buf["A_rows"], self._buf["l_rows"], self._buf["u_rows"] = (self._buf[k] for k in "Alu")
         return self._buf
 
     def _stage_input(self, t, shapes, name, device, dtype):
@@ -1174,11 +1424,12 @@ class BatchedLTVMPC(object):
     def _weights(self):
         return self.weights if self._stage_weights is None else self._stage_weights
 
-    def linearize(self, Ad, Bd, c=None, E=None, Q=None, R=None):
+    def linearize(self, Ad, Bd, c=None, E=None, Q=None, R=None, S=None):
         """New stage matrices Ad [B, N, nx, nx], Bd [B, N, nx, nu] (c [B, N, nx]): H and A of every instance are rebuilt on the
         device; the solver is set up on the first ``step`` (it needs g, l, u) and re-factored, state kept, afterwards.
         With ``stage_rows``: E [B, N, nc, nu + nx] or [N, nc, nu + nx], kept until replaced.
-        Stage weights Q [B, N, nx, nx] or [N, nx, nx], R [B, N, nu, nu] or [N, nu, nu]: kept until replaced."""
+        Stage weights Q [B, N, nx, nx] or [N, nx, nx], R [B, N, nu, nu] or [N, nu, nu]: kept until replaced.
+        Rate weight S [B, N, nu, nu], [N, nu, nu] or [nu, nu]: kept until replaced (before the first one: ``rate_weight``)."""
         import torch
         from reluqp import _cabi
         B, N, nx, nu = _ltv_shapes(Ad, Bd)
@@ -1209,27 +1460,46 @@ class BatchedLTVMPC(object):
             self._Qs, self._Rs = Qs, Rs
         if self._stage_weights is not None and self._stage_weights.batch not in (None, B):
             raise ValueError("the kept stage weights are for a batch of %d, the stages for %d" % (self._stage_weights.batch, B))
+        if S is not None and tuple(S.shape) not in ((B, N, nu, nu), (N, nu, nu), (nu, nu)):
+            raise ValueError("S has shape %s, expected %s, %s or %s" % (tuple(S.shape), (B, N, nu, nu), (N, nu, nu), (nu, nu)))
+        if S is None and self._S is not None and len(self._S.shape) == 4 and self._S.shape[0] != B:
+            raise ValueError("the kept rate weight is for a batch of %d, the stages for %d" % (self._S.shape[0], B))
         if not torch.cuda.is_available():
             raise _cabi.RqpUnavailable("BatchedLTVMPC needs a HIP device; the MI355X build has no CPU path")
         device, dtype = self._place()
         buf = self._buffers(B, device, dtype)
         to = lambda t: torch.as_tensor(t).to(device=device, dtype=dtype)
+        if S is not None:
+            self._S, self._S_dev = S, None
+        if self._S is not None and (self._S_dev is None or self._S_dev.shape[0] != B):
+            self._S_dev = rate_weight_device(self._S, nu, N, B, device)
         condense_ltv_device(to(Ad), to(Bd), self._weights(), buf["ws"], c=None if c is None else to(c), H=buf["H"],
-                            A=buf["A"] if nc is None else buf["A_box"])
+                            A=buf["A_rows"] if nc is None else buf["A_box"], S=self._S_dev)
         if nc is not None:
             if E is not None:
                 self._E = to(E).contiguous()
-            stage_rows_device((B, nx, nu, N), self._E, buf["ws"], A_c=buf["A"])
+            stage_rows_device((B, nx, nu, N), self._E, buf["ws"], A_c=buf["A_rows"])
+        if self.rate_rows:
+            buf["A"][:, :self.m_base].copy_(buf["A_base"])
+            rate_rows_device((B, nx, nu, N), buf["ws"], dtype, A_r=buf["A"], row0=self.m_base)
         self._lin = (c is not None,)
         if self._ready:
             self._handover(device)
             self.solver.update(Hx=buf["H"], Ax=buf["A"])
         return None
 
-    def qp_vectors(self, x, xref=None, uref=None, lo=None, hi=None):
+    def qp_vectors(self, x, xref=None, uref=None, lo=None, hi=None, u_prev=None, du_lo=None, du_hi=None):
         """(g, l, u) device tensors of the QPs for the states x [B, nx] under the current linearisation (``stage_rows``: with
-        the bounds lo, hi [B, N nc] or [N nc], kept until replaced)."""
+        the bounds lo, hi [B, N nc] or [N nc], kept until replaced; input rates: with u_prev [B, nu] and the rate bounds
+        du_lo, du_hi [B, N nu] or [N nu], kept until replaced)."""
         import torch
+        rate = self._S is not None or self.rate_rows
+        if not rate and (u_prev is not None or du_lo is not None or du_hi is not None):
+            raise ValueError("u_prev, du_lo, du_hi need BatchedLTVMPC(rate_weight=) / (du_max=) or linearize(S=)")
+        if not self.rate_rows and (du_lo is not None or du_hi is not None):
+            raise ValueError("du_lo, du_hi need BatchedLTVMPC(du_max=) (du_max=inf: rows whose bounds are given here)")
+        if rate and u_prev is None and self._uprev is None:
+            raise ValueError("input rates: the first step() needs u_prev")
         if self.stage_rows is not None and ((lo is None and self._lo is None) or (hi is None and self._hi is None)):
             raise ValueError("stage_rows: the first step() needs lo and hi")
         if self._lin is None:
@@ -1241,29 +1511,48 @@ class BatchedLTVMPC(object):
         if tuple(x.shape) != (buf["B"], self.nx):
             raise ValueError("x has shape %s, expected %s" % (tuple(x.shape), (buf["B"], self.nx)))
         nc = self.stage_rows
+        if nc is None and (lo is not None or hi is not None):
+            raise ValueError("lo, hi need BatchedLTVMPC(stage_rows=nc)")
+        if rate:
+            if u_prev is not None:
+                self._uprev = self._stage_input(u_prev, ((buf["B"], self.nu),), "u_prev", device, dtype)
+            elif tuple(self._uprev.shape) != (buf["B"], self.nu):
+                raise ValueError("the kept u_prev is for a batch of %d, the states for %d" % (self._uprev.shape[0], buf["B"]))
+            for name, t in (("du_lo", du_lo), ("du_hi", du_hi)):
+                if t is not None:
+                    setattr(self, "_" + name, self._stage_input(t, ((buf["B"], self.n), (self.n,)), name, device, dtype))
+        rate_kw = dict(S=self._S_dev, uprev=self._uprev) if self._S is not None else {}
         if nc is None:
-            if lo is not None or hi is not None:
-                raise ValueError("lo, hi need BatchedLTVMPC(stage_rows=nc)")
-            return ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
-                                      buf["u_add"], self._weights(), buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"], l=buf["l"],
-                                      u=buf["u"])
-        for name, t in (("lo", lo), ("hi", hi)):
-            if t is not None:
-                setattr(self, "_" + name, self._stage_input(t, ((buf["B"], self.m), (self.m,)), name, device, dtype))
-        if self._lo.dim() != self._hi.dim():
-            raise ValueError("lo and hi must both be [B, N nc] or both [N nc]")
-        g, _, _ = ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
-                                     buf["u_add"], self._weights(), buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"],
-                                     l=buf["l_box"], u=buf["u_box"])
-        l, u = stage_vectors_device((buf["B"], self.nx, self.nu, self.horizon), self._E, x, self._lo, self._hi, buf["ws"],
-                                    l_c=buf["l"], u_c=buf["u"])
+            g, l, u = ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
+                                         buf["u_add"], self._weights(), buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"],
+                                         l=buf["l_rows"], u=buf["u_rows"], **rate_kw)
+        else:
+            for name, t in (("lo", lo), ("hi", hi)):
+                if t is not None:
+                    setattr(self, "_" + name, self._stage_input(t, ((buf["B"], self.m_base), (self.m_base,)), name, device, dtype))
+            if self._lo.dim() != self._hi.dim():
+                raise ValueError("lo and hi must both be [B, N nc] or both [N nc]")
+            g, _, _ = ltv_vectors_device((self.nx, self.nu, self.horizon, self.K is not None, self._lin[0]), x, buf["l_add"],
+                                         buf["u_add"], self._weights(), buf["ws"], xref=to(xref), uref=to(uref), g=buf["g"],
+                                         l=buf["l_box"], u=buf["u_box"], **rate_kw)
+            l, u = stage_vectors_device((buf["B"], self.nx, self.nu, self.horizon), self._E, x, self._lo, self._hi, buf["ws"],
+                                        l_c=buf["l_rows"], u_c=buf["u_rows"])
+        if self.rate_rows:
+            dlo, dhi = (buf["du_lo"] if self._du_lo is None else self._du_lo), (buf["du_hi"] if self._du_hi is None else self._du_hi)
+            if dlo.dim() != dhi.dim():
+                raise ValueError("du_lo and du_hi must both be [B, N nu] or both [N nu]")
+            buf["l"][:, :self.m_base].copy_(buf["l_base"])
+            buf["u"][:, :self.m_base].copy_(buf["u_base"])
+            l, u = rate_bounds_device((buf["B"], self.nx, self.nu, self.horizon), x, self._uprev, dlo, dhi, buf["ws"], l_r=buf["l"],
+                                      u_r=buf["u"], row0=self.m_base)
         return g, l, u
 
-    def step(self, x, xref=None, uref=None, lo=None, hi=None):
+    def step(self, x, xref=None, uref=None, lo=None, hi=None, u_prev=None, du_lo=None, du_hi=None):
         """One control step for the states x [B, nx] (references xref [B, N, nx] for x_1 .. x_N, uref [B, N, nu]; with
-        ``stage_rows`` the bounds lo, hi): returns (u_0 [B, nu] device tensor, Results)."""
+        ``stage_rows`` the bounds lo, hi; with input rates u_prev [B, nu], required on the first step, afterwards the u_0 the
+        previous step returned unless given, and the rate bounds du_lo, du_hi): returns (u_0 [B, nu] device tensor, Results)."""
         import torch
-        g, l, u = self.qp_vectors(x, xref, uref, lo, hi)
+        g, l, u = self.qp_vectors(x, xref, uref, lo, hi, u_prev, du_lo, du_hi)
         device, dtype = self._place()
         buf = self._buf
         self._handover(device)
@@ -1281,19 +1570,22 @@ class BatchedLTVMPC(object):
         v0 = res.x[:, :self.nu].to(device)
         x = torch.as_tensor(x).to(device=device, dtype=dtype)
         u0 = v0.clone() if buf["Kt"] is None else v0 - x @ buf["Kt"]      # (never a view of the solver's result buffer)
+        if self._S is not None or self.rate_rows:
+            self._uprev = u0.detach().clone()  # the next step's u_{-1} (the caller may change u0)
         return u0, res
 
-    def simulate(self, x0, steps, plant, relinearize_every=1, xref=None, uref=None):
+    def simulate(self, x0, steps, plant, relinearize_every=1, xref=None, uref=None, u_prev=None):
         """Closed loop on the device: ``plant(x, u) -> (x_next, Ad, Bd, c)`` is a torch callable returning the next states and
         the linearisation to use from them (Ad [B, N, nx, nx], Bd [B, N, nx, nu], c [B, N, nx] or None).  The linearisation
         is refreshed every ``relinearize_every`` steps; ``linearize()`` must have been called for the first one.
+        Input rates: ``u_prev`` [B, nu] is the input applied before the first step; every later step starts from the one before.
         Returns (states [steps + 1, B, nx], inputs [steps, B, nu], iterations [steps, B]) as device tensors."""
         import torch
         device, dtype = self._place()
         x = torch.as_tensor(x0).to(device=device, dtype=dtype)
         xs, us, its = [x], [], []
         for k in range(steps):
-            u0, res = self.step(x, xref=xref, uref=uref)
+            u0, res = self.step(x, xref=xref, uref=uref, u_prev=u_prev if k == 0 else None)
             x, Ad, Bd, c = plant(x, u0)
             if (k + 1) % relinearize_every == 0 and k + 1 < steps:
                 self.linearize(Ad, Bd, c)

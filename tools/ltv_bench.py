@@ -13,9 +13,15 @@ box as nu rows of E plus nc - nu random half-planes per stage) next to the same 
 Stage-weight columns (--stage-weights): `condense`, `vectors` (with xref: the call that reads the weights) and the adjoint with
 Q [B, N, nx, nx], R [B, N, nu, nu] (RQP_LTV_STAGE_WEIGHTS) next to the shared-weight calls of the same run, the two alternating
 call by call (medians of --reps each), on a workspace of their own.
+Input-rate columns (--rate): `condense` with a rate weight S [B, N, nu, nu] (rqp_ltv_condense_rate) and `vectors` with it
+(rqp_ltv_vectors_rate) next to the plain calls of the same run, alternating call by call, on a workspace of their own;
+rqp_ltv_rate_rows and rqp_ltv_rate_bounds written into the tail of [B, m + N nu, ...] tensors; the driver's strided copy of the m
+base rows into that tensor; and update(Hx, Ax) + warm solve() of a BatchedLTVMPC(stage_rows=nc, du_max=) handle (m_c + N nu rows)
+next to the same two of the stage handle (m_c rows).
 Per-kernel times (k_ltv_transition among them): run the same command under `rocprofv3 --kernel-trace --stats`.
 
-    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--stage-weights] [--out profiles/r8_ltv/ltv_bench.json]
+    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--stage-weights] [--rate] [--out profiles/r8_ltv/ltv_bench.json]
+        [--rate-out profiles/r12_ltv_rate/ltv_rate_bench.json]
         [--stage-out profiles/r10_ltv_stage/ltv_stage_bench.json] [--stage-weights-out profiles/r11_ltv_stage_cost/ltv_stage_cost_bench.json]
 """
 import argparse
@@ -101,6 +107,9 @@ def main():
     ap.add_argument("--stage-weights", action="store_true",
                     help="add the stage-weight columns: condense, vectors and the adjoint with per-(instance, stage) Q, R")
     ap.add_argument("--stage-weights-out", default=os.path.join(REPO, "profiles", "r11_ltv_stage_cost", "ltv_stage_cost_bench.json"))
+    ap.add_argument("--rate", action="store_true",
+                    help="add the input-rate columns: condense / vectors with a rate weight, the rate rows and bounds, the base-row copy")
+    ap.add_argument("--rate-out", default=os.path.join(REPO, "profiles", "r12_ltv_rate", "ltv_rate_bench.json"))
     args = ap.parse_args()
     if not NU <= args.stage_rows <= 32:
         ap.error("--stage-rows must be in [%d, 32]: the input box takes %d rows of E, the kernels hold 32" % (NU, NU))
@@ -172,6 +181,40 @@ def main():
                 out["ab_%s_stage_over_shared" % name] = b[0] / a[0]
             ctl.qp_vectors(xt)                 # (the driver's g, l, u as the columns below expect them)
             del sw, ws2, H2, A2, g2, l2, u2
+        if args.rate:                          # condense / vectors with a rate weight, alternating with the plain calls
+            Sr = _stage_weights(np.random.RandomState(3), B)[1]
+            Sd = mpc.rate_weight_device(Sr, NU, N, B, dev)
+            del Sr
+            ws2 = mpc.ltv_workspace(B, NX, NU, N, dev)
+            H2, A2 = torch.empty_like(buf["H"]), torch.empty_like(buf["A"])
+            g2, l2, u2 = torch.empty_like(buf["g"]), torch.empty_like(buf["l"]), torch.empty_like(buf["u"])
+            up = t(0.1 * rs.randn(B, NU))
+            d5, d4r = (NX, NU, N, True, False), (B, NX, NU, N)
+            cond_r = lambda: mpc.condense_ltv_device(Adt, Bdt, ctl.weights, ws2, H=H2, A=A2, S=Sd)
+            vec_p = lambda: mpc.ltv_vectors_device(d5, xt, buf["l_add"], buf["u_add"], ctl.weights, buf["ws"], g=buf["g"], l=buf["l"],
+                                                   u=buf["u"])
+            vec_r = lambda: mpc.ltv_vectors_device(d5, xt, buf["l_add"], buf["u_add"], ctl.weights, ws2, g=g2, l=l2, u=u2, S=Sd, uprev=up)
+            cond_r()
+            for name, fa, fb in (("condense", cond, cond_r), ("vectors", vec_p, vec_r)):
+                a, b = _timed_ab(torch, fa, fb, args.reps)
+                out["rate_ab_%s_plain_ms" % name], out["rate_ab_%s_plain_min_ms" % name], out["rate_ab_%s_plain_max_ms" % name] = a
+                out["rate_ab_%s_rate_ms" % name], out["rate_ab_%s_rate_min_ms" % name], out["rate_ab_%s_rate_max_ms" % name] = b
+                out["rate_ab_%s_rate_minus_plain_ms" % name] = b[0] - a[0]
+            # k_rate_w moves the u rows of W (read, write) and of F (read): 3 x 8 N nu n bytes per instance
+            out["rate_w_bytes_estimate"] = 3 * 8 * N * NU * ctl.n * B
+            mt, nr = ctl.m + ctl.n, ctl.n
+            At = torch.empty(B, mt, ctl.n, dtype=prec, device=dev)
+            lt, ut = torch.empty(B, mt, dtype=prec, device=dev), torch.empty(B, mt, dtype=prec, device=dev)
+            dl = t(np.full(nr, 0.2))
+            out["rate_rows_ms"], out["rate_rows_min_ms"], out["rate_rows_max_ms"] = _timed(
+                torch, lambda: mpc.rate_rows_device(d4r, buf["ws"], prec, A_r=At, row0=ctl.m), args.reps)
+            out["rate_bounds_ms"], out["rate_bounds_min_ms"], out["rate_bounds_max_ms"] = _timed(
+                torch, lambda: mpc.rate_bounds_device(d4r, xt, up, -dl, dl, buf["ws"], l_r=lt, u_r=ut, row0=ctl.m), args.reps)
+            out["rate_base_row_copy_ms"], out["rate_base_row_copy_min_ms"], out["rate_base_row_copy_max_ms"] = _timed(
+                torch, lambda: At[:, :ctl.m].copy_(buf["A"]), args.reps)
+            out["rate_base_row_copy_bytes"] = 2 * B * ctl.m * ctl.n * At.element_size()
+            ctl.qp_vectors(xt)
+            del Sd, ws2, H2, A2, g2, l2, u2, At, lt, ut
         # (a second handle on the same data: the columns above stay those of a handle without the adjoint's workspace)
         sd = reluqpth.ReLU_QP()
         sd.setup(buf["H"], buf["g"], buf["A"], buf["l"], buf["u"], device=dev, precision=prec, eps_abs=1e-3, differentiable=True)
@@ -216,6 +259,22 @@ def main():
             ss.update(g=sbuf["g"], l=sbuf["l"], u=sbuf["u"])
             ss.solve()
         out["stage_warm_solve_ms"], _, _ = _timed(torch, stage_warm_solve, args.reps)
+        if args.rate:                          # the same handle with N nu rate rows behind the stage rows
+            rctl = mpc.BatchedLTVMPC(NX, NU, N, Q, R, P, K=K, stage_rows=nc, du_max=0.2, rate_weight=0.05 * np.eye(NU), device=dev,
+                                     precision=prec, eps_abs=1e-3)
+            rctl.linearize(Adt, Bdt, E=Et)
+            rctl.step(xt, lo=lot, hi=hit, u_prev=t(np.zeros((B, NU))))
+            rs_, rbuf = rctl.solver, rctl._buf
+            out["rate_m"], out["rate_kernel"] = rctl.m, rs_.kernel
+            rs_.synchronous = False
+            out["rate_update_mats_ms"], _, _ = _timed(torch, lambda: rs_.update(Hx=rbuf["H"], Ax=rbuf["A"]), args.reps)
+            rctl.qp_vectors(xt)
+
+            def rate_warm_solve():
+                rs_.update(g=rbuf["g"], l=rbuf["l"], u=rbuf["u"])
+                rs_.solve()
+            out["rate_warm_solve_ms"], _, _ = _timed(torch, rate_warm_solve, args.reps)
+            del rctl, rs_, rbuf
         del sctl, ss, sbuf, Et
         del adj_ws, cot
         torch.cuda.synchronize()
@@ -242,6 +301,12 @@ def main():
     os.makedirs(os.path.dirname(args.stage_out), exist_ok=True)
     with open(args.stage_out, "w") as f:
         json.dump(dict(device=torch.cuda.get_device_name(0), results=stage), f, indent=1)
+    if args.rate:
+        rt = [{k: v for k, v in r.items() if k in keep or k.startswith("rate_") or k in ("stage_update_mats_ms", "stage_warm_solve_ms",
+                                                                                        "m_c", "stage_rows_ms")} for r in res]
+        os.makedirs(os.path.dirname(args.rate_out), exist_ok=True)
+        with open(args.rate_out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), results=rt), f, indent=1)
     if args.stage_weights:
         sw = [{k: v for k, v in r.items() if k in keep or k.startswith("ab_")} for r in res]
         os.makedirs(os.path.dirname(args.stage_weights_out), exist_ok=True)
