@@ -100,6 +100,14 @@ struct Res2Cfg {
     // the 8 column groups a wave reads together (SW*(cc>>1) + CQ*(cc&1)) fall in distinct LDS banks
     static constexpr int SW = 8 * KR + 4;
     static constexpr int ND = NW * SW;           // padded vector length
+    // dvec, dxv and gT -- the vectors the solve loop reads through ds_read2_b32, whose two offsets reach 255 dwords from the
+    // lane's base -- open the LDS image, so that every such address is lane base + immediate.  Where the three do not fit
+    // into that reach back to back they are interleaved by wave block, [wave][dvec dxv gT][SW]: slot i of array a then sits
+    // at TW*(i/SW) + TA*a + i%SW.  (KR = 4: block pitch 108 dwords, the 8 groups of a K d read start at 0,13,108,121,216,229,
+    // 324,337 and 0,10,108,118,.. -- distinct banks mod 32 and mod 64, as with the plain pitch SW; KR = 2: plain.)
+    static constexpr bool TRI = 2 * ND + CQ - 1 > 255;   // (the farthest immediate of the plain layout: gT's)
+    static constexpr int TW = TRI ? 3 * SW : SW; // pitch of a wave block of dvec / dxv / gT
+    static constexpr int TA = TRI ? SW : ND;     // distance between the three arrays
     static constexpr int AE2 = RP * CQ;          // A float2 pairs per thread
     static constexpr int KE2 = KP * KC;          // K / H float2 pairs per thread
     static constexpr int HR = 4, HP = HR / 2;    // H rows per row group in the transposed product (PL*HR >= N)
@@ -112,9 +120,10 @@ struct Res2Cfg {
     static_assert(RB % 2 == 0 && KR % 2 == 0 && HP == 2 && HU == CQ && PL * HR >= N, "row pairs");
     static_assert(8 * KR >= CW && 8 * KC >= N && M <= 2 * NT && KC == CQ && NQ == 2, "tile shape");
     static constexpr size_t lds_bytes() {
-        return (size_t)M * 8 * 4 + ND * 8 + 16 * 8       // zt64 lam64 z64 inv64 | x64 | redd
-               + (size_t)M * 4 * 5                       // lT uT rv32 nu cT
-               + (size_t)ND * 4 * 6                      // xin xnat dxv hx gT dvec
+        return (size_t)ND * 4 * 3 + (size_t)M * 4 + ND * 4      // dvec dxv gT | nu | xin
+               + (size_t)M * 8 * 4 + ND * 8 + 16 * 8     // zt64 lam64 z64 inv64 | x64 | redd
+               + (size_t)M * 4 * 4                       // lT uT rv32 cT
+               + (size_t)ND * 4 * 2                      // xnat (with its zero tail)
                + (size_t)NW * M * 4 + 96 * 4             // part, red (two check buffers + the rho ladder)
                + (size_t)HU * NT * 16;                   // Hs
     }
@@ -134,9 +143,18 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
                                                       const float* __restrict__ Hpack, unsigned long long* dbg,
                                                       const float* __restrict__ Kscale) {
     constexpr int RB = C::RB, CQ = C::CQ, KR = C::KR, KC = C::KC, NT = C::NT, NW = C::NW, RP = C::RP, KP = C::KP;
-    constexpr int CW = C::CW, M = C::M, ND = C::ND, SW = C::SW, AE2 = C::AE2, KE2 = C::KE2, HU = C::HU, HP = C::HP, HR = C::HR, H1 = C::H1, H2 = C::H2;
+    constexpr int CW = C::CW, M = C::M, ND = C::ND, SW = C::SW, TW = C::TW, TA = C::TA, AE2 = C::AE2, KE2 = C::KE2, HU = C::HU, HP = C::HP, HR = C::HR, H1 = C::H1, H2 = C::H2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    double* zt64 = (double*)smem_raw;                    // [M] A x        (row i owned by thread i % 256)
+    // The arrays the solve loop reaches through the 8-bit-offset LDS forms come first, inside those forms' range of the lane's
+    // base address: dvec / dxv / gT (ds_read2_b32: 255 dwords) and nu (ds_read2_b64: 255 x 8 bytes)
+    float* dvec = (float*)smem_raw;                       // [ND] d; H x from a check on    } slot i at tslot(i):
+    float* dxv = dvec + TA;                               // [ND] dx                         } Res2Cfg::TRI
+    float* gT = dxv + TA;                                 // [ND]                            }
+    float* nu = dvec + 3 * ND;                            // [M] nu (lam at a check)
+    float* xin = nu + M;                                  // [ND] float(x) of the INCOMING state, slot order (the loop keeps x64 and xnat)
+    // (xin here puts the row arrays where the paired stride-64 reads of the row pass reach them from tid * 8 and tid * 4 without
+    //  an address add: on the big tile the doubles start at 7 * 512 bytes, the float rows at 59 * 256)
+    double* zt64 = (double*)(xin + ND);                   // [M] A x        (row i owned by thread i % 256)
     double* lam64 = zt64 + M;
     double* z64 = lam64 + M;
     double* inv64 = z64 + M;                              // 1 / rho_i
@@ -145,20 +163,26 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
     float* lT = (float*)(redd + 16);                      // [M]
     float* uT = lT + M;
     float* rv32 = uT + M;
-    float* nu = rv32 + M;                                 // [M] nu (lam at a check)
-    float* cT = nu + M;                                   // [M] c_i (1 in the padding rows): rho_i = rho c_i at a rho move
-    float* xin = cT + M;                                  // [ND] float(x), slot order (SW per wave)
-    float* xnat = xin + ND;                               // [ND] float(x), natural order (rows of H)
-    float* dxv = xnat + ND;                               // [ND] dx
-    float* hx = dxv + ND;                                 // [ND] H x
-    float* gT = hx + ND;                                  // [ND]
-    float* dvec = gT + ND;                                // [ND] d (A' lam at a check)
-    float* part = dvec + ND;                              // [NW][M] per-wave partial row sums of A dx
+    float* cT = rv32 + M;                                 // [M] c_i (1 in the padding rows): rho_i = rho c_i at a rho move
+    float* xnat = cT + M;                                 // [2 ND] float(x), natural order (rows of H), zeros from ND on: the transposed
+                                                          //  product reads HR * PL entries (the tail meets zero rows of the H image, and
+                                                          //  0 * x must be 0: no stale LDS there)
+    float* hx = dvec;                                     // H x: d lives from B3 to B2 of one iteration, H x from a check to the next B3
+    float* part = xnat + 2 * ND;                          // [NW][M] per-wave partial row sums of A dx
+    static_assert(2 * ND >= C::PL * HR, "xnat covers the H rows of every lane group");
     float* red = part + NW * M;                           // [96]: two [NW][8] check buffers (by check parity), the rho ladder
     float* Hs = red + 96;                                 // [HU][NT][4]
-    static_assert(((size_t)M * 8 * 4 + ND * 8 + 16 * 8 + (size_t)M * 4 * 5 + ND * 4 * 6 + NW * M * 4 + 96 * 4) % 16 == 0,
-                  "H image must start 16-byte aligned");
-
+    static_assert(((size_t)ND * 4 * 4 + M * 4) % 16 == 0 && ((size_t)M * 8 * 4 + ND * 8 + 16 * 8 + (size_t)M * 4 * 4) % 16 == 0 &&
+                      ((size_t)ND * 4 * 2 + NW * M * 4 + 96 * 4) % 16 == 0,
+                  "the doubles, xnat and the H image must start 16-byte aligned");
+    static_assert(3 * ND * 4 + (RP - 1) * 8 <= 255 * 8 && 2 * TA + CQ - 1 <= 255, "nu / gT within reach of the ds_read2 offsets");
+    auto tslot = [](int i) { return C::TRI ? i + (TW - SW) * (i / SW) : i; };   // slot i of dvec / dxv / gT
+    auto tslot_o = [&]() {                               // ... of slot tid, outside the solve loop: formed on the spot from an opaque
+        if constexpr (!C::TRI) return (int)threadIdx.x;   // copy of tid, so that it is not kept in a register across the loop
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return t + (TW - SW) * (t / SW);
+    };
     const int n = a.n, m = a.m;
     const int b = a.order ? a.order[blockIdx.x] : (int)blockIdx.x, tid = threadIdx.x;   // dispatch order: longest solve first
     const int wave = tid >> 6, lane = tid & 63;
@@ -302,10 +326,10 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         x64[i] = xv;
         xin[i] = (float)xv;
         xnat[i] = (i < n) ? (float)a.x[(size_t)b * n + i] : 0.f;
-        gT[i] = in ? ((const float*)a.g)[(size_t)b * n + col] : 0.f;
-        hx[i] = 0.f;
-        dxv[i] = 0.f;
-        dvec[i] = 0.f;
+        xnat[ND + i] = 0.f;
+        gT[tslot(i)] = in ? ((const float*)a.g)[(size_t)b * n + col] : 0.f;
+        dxv[tslot(i)] = 0.f;
+        dvec[tslot(i)] = 0.f;
     }
 
     // where this lane deposits its share of the A' reduce-scatter: columns colw .. colw + ncolw - 1
@@ -316,15 +340,15 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         int nval = b4 ? (H1 - H2) : H2;                   // entries that are not step-B duplicates
         if (b5 && cbase + nval > CQ) nval = CQ - cbase;   // ... nor step-A duplicates
         ncolw = ((lane & 0xE) == 0) ? nval : 0;           // one writer per (q, class): lane bits 1..3 == 0
-        colw = SW * wave + CQ * q + cbase;
+        colw = TW * wave + CQ * q + cbase;                 // (in dvec / dxv / gT: pitch TW)
     }
     __syncthreads();
 
     // ---- products ------------------------------------------------------------------------------------
     // wave partial of A v over the wave's CW columns -> part[wave][row]   (v: this wave's CW entries)
-    auto load_vc = [&](const float* v, float (&vc)[CQ]) __attribute__((always_inline)) {
+    auto load_vc = [&](const float* v, int pitch, float (&vc)[CQ]) __attribute__((always_inline)) {     // pitch: SW (xin), TW (dxv)
 #pragma unroll
-        for (int c = 0; c < CQ; ++c) vc[c] = v[SW * wave + CQ * q + c];
+        for (int c = 0; c < CQ; ++c) vc[c] = v[pitch * wave + CQ * q + c];
     };
     auto prod_A = [&](const float (&vc)[CQ]) __attribute__((always_inline)) {
         f2 acc[RP];
@@ -509,11 +533,12 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
                 }
         }
     };
-    // y[CW*wave + KR*rr + r] = sum_c Mat[..][KC*cc + c] * v[KC*cc + c] summed over cc; lanes cc == 0 get the sums
+    // y[CW*wave + KR*rr + r] = sum_c Mat[..][KC*cc + c] * v[KC*cc + c] summed over cc by a butterfly: EVERY lane
+    // of the group of 8 ends up with all KR sums (the x update relies on it: lane cc = r takes row r)
     auto prod_K = [&](const float* v, float (&s)[KR]) {
         float vc[KC];
 #pragma unroll
-        for (int c = 0; c < KC; ++c) vc[c] = v[SW * (cc >> 1) + CQ * (cc & 1) + c];
+        for (int c = 0; c < KC; ++c) vc[c] = v[TW * (cc >> 1) + CQ * (cc & 1) + c];      // (v = dvec: pitch TW)
 #pragma unroll
         for (int kp = 0; kp < KP; ++kp) {
             f2 t = {0.f, 0.f};
@@ -655,7 +680,7 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
     // ---- A x of the incoming state (an exact continuation brought it along: only lam_hat / nu of the next iteration are due)
     if (!exact) {
         float vc0[CQ];
-        load_vc(xin, vc0);
+        load_vc(xin, SW, vc0);
         prod_A(vc0);
         __syncthreads();
         row_pass(true, false, kmax > k0);
@@ -663,7 +688,7 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         row_pass(false, false, kmax > k0);
     }
 
-    // ---- compute_residuals (reluqpth.py:307-318) on the current state (hx = H x valid)
+    // ---- compute_residuals (reluqpth.py:307-318) on the current state; leaves H x in hx (= d's array)
     float scl_p = 0.f, scl_d = 0.f;                                    // residual scales of the last check (eps_rel)
     // the row part for the call sites without a preceding row pass (mode 2; the final call after max_iter)
     auto res_rows = [&]() {
@@ -693,8 +718,8 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         __syncthreads();
         stamp(10);
         if (tid < ND && (tid % SW) >= CW) {                              // padding slots: exact zeros
-            dxv[tid] = 0.f;
-            hx[tid] = 0.f;
+            dxv[tslot_o()] = 0.f;
+            hx[tslot_o()] = 0.f;
         }
         prod_At_chk(nu, dxv, hx);                                      // t3 = A' lam (dxv is dead here: scratch), t2 = H x
         stamp(11);
@@ -706,11 +731,12 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
                 const int col = CW * (tid_w / SW) + (tid_w % SW);
                 if ((tid_w % SW) < CW && col < n) wd = (float)(1.0 / (a.scC[mat] * a.scD[mat * n + col]));
             }
-            const float t3 = dxv[tid];
-            v[3] = fabsf(hx[tid] + t3 + gT[tid]) * wd;
-            v[4] = fabsf(hx[tid]) * wd;
+            const int ts = tslot_o();
+            const float t3 = dxv[ts], t2 = hx[ts];
+            v[3] = fabsf(t2 + t3 + gT[ts]) * wd;
+            v[4] = fabsf(t2) * wd;
             v[5] = fabsf(t3) * wd;
-            v[6] = fabsf(gT[tid]) * wd;
+            v[6] = fabsf(gT[ts]) * wd;
         }
         // Wave max of the 7 values + NaN mask (torch max/norm propagate NaN).  The mask bit of a value is a wave-wide "any lane":
         // the compare already delivers it as a lane mask, no cross-lane step.  The maxima (v_max, IEEE maxNum: exactly associative
@@ -783,36 +809,28 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
         {
             float s[KR];
             static_assert(KR == 4 || KR == 2, "vectorised x update");
-            const int j = SW * wave + KR * rr;
-            double2* xp = (double2*)(x64 + j);
-            double2 xold[KR / 2];                                      // x of this lane's slots: requested before the products
-#pragma unroll
-            for (int hlf = 0; hlf < KR / 2; ++hlf) xold[hlf] = xp[hlf];
+            // After the butterfly of prod_K every lane of a group of 8 holds all KR sums: lane cc = r < KR takes row r and
+            // updates the one slot KR rr + r (one float64 chain per lane on KR lanes of 8, not KR chains on one lane)
+            const int jr = KR * rr + cc;                               // (lanes cc < KR)
+            double* xp = x64 + SW * wave + jr;
+            double xa = 0.0;
+            if (cc < KR) xa = *xp;                                     // x of this lane's slot: requested before the products
             prod_K(dvec, s);                                           // K d
+            float sr = s[0];
+#pragma unroll
+            for (int r = 1; r < KR; ++r) sr = (cc == r) ? s[r] : sr;
             // dx goes to LDS first and the A dx operands are requested right behind it: the float64 x update below runs
             // while that same-wave LDS hop is in flight (LDS operations of a wave execute in order: behind the x stores the
             // reads would wait for them too)
-            if (cc == 0) {                 // this lane owns slots j..j+3 (rows >= CW of the group: zero rows of K, padding slots)
-#pragma unroll
-                for (int hlf = 0; hlf < KR / 2; ++hlf) ((f2*)(dxv + j))[hlf] = (f2){-s[2 * hlf], -s[2 * hlf + 1]};
-            }
+            if (cc < KR) dxv[TW * wave + jr] = -sr;     // (rows >= CW of the wave: zero rows of K, padding slots)
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // dx of this wave's columns: same-wave LDS hop
             __builtin_amdgcn_wave_barrier();
             float vc[CQ];
-            load_vc(dxv, vc);
-            if (cc == 0) {
-                f2* xn2 = (f2*)(xnat + CW * wave + KR * rr);                   // natural order: real columns only
-#pragma unroll
-                for (int hlf = 0; hlf < KR / 2; ++hlf) {
-                    double2 xa = xold[hlf];
-                    const f2 dx = {-s[2 * hlf], -s[2 * hlf + 1]};
-                    xa.x += (double)dx.x;
-                    xa.y += (double)dx.y;
-                    xp[hlf] = xa;
-                    const f2 xf = {(float)xa.x, (float)xa.y};
-                    ((f2*)(xin + j))[hlf] = xf;
-                    if (KR * rr + 2 * hlf + 1 < CW) xn2[hlf] = xf;
-                }
+            load_vc(dxv, TW, vc);
+            if (cc < KR) {
+                xa += (double)(-sr);
+                *xp = xa;
+                if (jr < CW) xnat[CW * wave + jr] = (float)xa;         // natural order: real columns only
             }
             stamp(3);
             prod_A(vc);                                                // partial A dx
@@ -923,8 +941,11 @@ __global__ void __launch_bounds__(256, C::WAVES_PER_SIMD) k_admm_res2(SolveArgs 
     }            // :243 (Q11 fixed: fresh state)
 
     // objective 1/2 x'Hx + g'x (compute_J :320-322)
+    // hx shares d's array: it holds H x of the FINAL state only because every way here runs residuals() behind the last prod_At
+    // (the converged break leaves the loop right behind a check; otherwise residuals() has just run above).  A new loop exit
+    // that reaches this point must keep that.
     double jp = 0.0;
-    if (tid < ND) jp = (double)(xin[tid] * (0.5f * hx[tid] + gT[tid]));
+    if (tid < ND) jp = (double)((float)x64[tid] * (0.5f * hx[tslot_o()] + gT[tslot_o()]));      // (x64: xin is not kept up in the loop)
     for (int off = 32; off >= 1; off >>= 1) jp += __shfl_xor(jp, off, 64);
     if (lane == 0) redd[wave] = jp;
     __syncthreads();
