@@ -540,10 +540,11 @@ int rqp_ltv_stage_adjoint(const rqp_ltv_dims* dims, int device, int32_t nc, cons
  * uprev among them) is NULL.
  *
  * A workspace written by rqp_ltv_condense_rate holds W_rate and gmap of the rate problem.  It must be read by
- * rqp_ltv_vectors_rate, not rqp_ltv_vectors (which would leave S_0 uprev out of g), and it must not be given to
- * rqp_ltv_condense_adjoint: reverse mode of the rate terms is not implemented.  F and [G | f] in it are those of
- * rqp_ltv_condense: the rqp_ltv_stage_* calls, rqp_ltv_rate_rows and rqp_ltv_rate_bounds read only them and work on the
- * workspace of either condense call.  The plain entry points and their launch chains are unchanged.                          */
+ * rqp_ltv_vectors_rate, not rqp_ltv_vectors (which would leave S_0 uprev out of g), and its reverse mode is
+ * rqp_ltv_condense_adjoint_rate (below), not rqp_ltv_condense_adjoint, which reads W as H_sp F and knows no rate term.  F and
+ * [G | f] in it are those of rqp_ltv_condense: the rqp_ltv_stage_* calls, rqp_ltv_rate_rows, rqp_ltv_rate_bounds and
+ * rqp_ltv_condense_adjoint_rate read only them and work on the workspace of either condense call.  The plain entry points and
+ * their launch chains are unchanged.                                                                                         */
 int rqp_ltv_condense_rate(const rqp_ltv_dims* dims, int device, const void* Ad, const void* Bd, const void* c,
                           const double* Q, const double* R, const double* Qf, const double* K, const double* S,
                           void* H, void* A, void* workspace, void* stream);
@@ -558,6 +559,40 @@ int rqp_ltv_vectors_rate(const rqp_ltv_dims* dims, int device, const void* x0, c
 int rqp_ltv_rate_rows(const rqp_ltv_dims* dims, int device, const void* workspace, void* A_r, int64_t inst_stride, void* stream);
 int rqp_ltv_rate_bounds(const rqp_ltv_dims* dims, int device, const void* x0, const void* uprev, const void* dlo,
                         const void* dhi, const void* workspace, void* l_r, void* u_r, int64_t inst_stride, void* stream);
+
+/* Reverse mode of the rate terms (DESIGN.md section 5 "LTV condensing, input rates, adjoint"): rqp_ltv_condense_adjoint for a
+ * problem built by rqp_ltv_condense_rate + rqp_ltv_vectors_rate (+ rqp_ltv_rate_rows + rqp_ltv_rate_bounds).  io is that call's:
+ * dH, dg are the cotangents of the rate problem's H and g, dA, dl, du those of the base rows (A = F and the box, or the dA_full /
+ * dl_full of rqp_ltv_stage_adjoint); rate_io adds S, uprev, the cotangents of (A_r, l_r, u_r) and the outputs dS, duprev.  With
+ * dF_k, ds_k as above, Hs = (dH + dH') / 2, q_k = (F dg)[u_k] - (F dg)[u_{k-1}], r_k = ds_k - [k = 0] uprev, t = dl_r + du_r and
+ * M_k = dF_k Hs, the formulas of rqp_ltv_condense_adjoint gain
+ *     Fb[u_k rows] += Z_k - Z_{k+1},   Z_k = dA_r,k + S_k (2 M_k + r_k dg')   (Z_N = 0),
+ *     sb[u_k rows] += w_k - w_{k+1},   w_k = S_k q_k - t_k   (w_N = 0; before dx0 = G'sb and [Gb | fb] = sb [x0' | 1]),
+ *     dS_k = sym(M_k dF_k' + q_k r_k')  (per instance and stage, bitwise symmetric),   duprev = t_0 - S_0 q_0;
+ * eb = H_sp F dg (dxref, duref) and Sb_kk (dQ, dR, dQf) are those of the plain call: dQ, dR, dQf come back with its bits.  The
+ * gradients of dlo, dhi are dl_r, du_r themselves.  The rate addend to Fb is formed and added in float64 whatever dims.dtype.
+ * Whatever finite values dA_r holds right of the staircase (columns >= (k + 1) nu of block row k) are not read.
+ * io->workspace may come from rqp_ltv_condense or rqp_ltv_condense_rate of this linearisation: only F and [G | f] are read.
+ * io->adjoint_workspace needs rqp_ltv_adjoint_rate_workspace_bytes (that of the plain call and 2 horizon nu doubles per instance).
+ * dA_r / dl_r, du_r: instance b starts dA_stride / dl_stride ELEMENTS after instance b - 1, as inst_stride of the forward row
+ * calls, so they can be the tails of [batch][m0 + horizon nu][n] and [batch][m0 + horizon nu] cotangents; a stride is checked
+ * only when one of its pointers is given (smaller than one instance's rows: RQP_ERR_ARG; more than 640 rows: RQP_ERR_UNSUPPORTED).
+ * The contract of the other rqp_ltv_* calls holds: float64 arithmetic, every output rounded once, no allocation, no host
+ * synchronisation, no atomics, no scratch, a launch chain fixed by dims and by which pointers are NULL (that of
+ * rqp_ltv_condense_adjoint with its first kernel replaced and one kernel added before the sweep; capturable in a HIP graph), the
+ * caller's current device restored, rqp_last_error(NULL).  RQP_ERR_ARG: what rqp_ltv_condense_adjoint rejects, or rate_io, S or
+ * uprev NULL.  RQP_ERR_UNSUPPORTED: the sizes of rqp_ltv_condense_rate.                                                       */
+typedef struct rqp_ltv_rate_adjoint_io {
+    const double* S;             /* [batch][horizon][nu][nu] double, as in rqp_ltv_condense_rate                          */
+    const void* uprev;           /* [batch][nu]                                                                           */
+    const void *dA_r, *dl_r, *du_r; /* cotangents of the rate rows: horizon nu rows of n / horizon nu entries; NULL = 0   */
+    int64_t dA_stride, dl_stride;/* elements between the instances of dA_r, and of dl_r / du_r                            */
+    double* dS;                  /* output [batch][horizon][nu][nu], no batch sum; NULL = not wanted                      */
+    void* duprev;                /* output [batch][nu]; NULL = not wanted                                                 */
+} rqp_ltv_rate_adjoint_io;
+int rqp_ltv_adjoint_rate_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes);
+int rqp_ltv_condense_adjoint_rate(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io,
+                                  const rqp_ltv_rate_adjoint_io* rate_io, void* stream);
 
 /* Which solve kernel the handle dispatches to ("generic", "resident", ...).       */
 const char* rqp_kernel_name(const rqp_handle* h);

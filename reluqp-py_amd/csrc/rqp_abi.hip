@@ -1316,6 +1316,41 @@ int rqp_ltv_rate_bounds(const rqp_ltv_dims* dims, int device, const void* x0, co
     return RQP_OK;
 }
 
+int rqp_ltv_adjoint_rate_workspace_bytes(const rqp_ltv_dims* dims, size_t* bytes) {
+    ltv_err.clear();
+    if (!bytes) return ltv_fail(RQP_ERR_ARG, "rqp_ltv_adjoint_rate_workspace_bytes: bytes is NULL");
+    if (int rc = ltv_rate_check(dims, "rqp_ltv_adjoint_rate_workspace_bytes")) return rc;
+    *bytes = rqp_ltv_rate_adj_ws_bytes(dims);
+    return RQP_OK;
+}
+
+int rqp_ltv_condense_adjoint_rate(const rqp_ltv_dims* dims, int device, const rqp_ltv_adjoint_io* io,
+                                  const rqp_ltv_rate_adjoint_io* rate_io, void* stream) {
+    const char* fn = "rqp_ltv_condense_adjoint_rate";
+    ltv_err.clear();
+    if (int rc = ltv_rate_check(dims, fn)) return rc;
+    const bool staged = (dims->flags & RQP_LTV_STAGE_WEIGHTS) != 0;
+    if (!io || !io->Ad || !io->Bd || !io->x0 || !io->Q || !io->R || (!staged && !io->Qf) || !io->workspace || !io->adjoint_workspace)
+        return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": io, Ad, Bd, x0, Q, R, Qf, workspace and adjoint_workspace are required");
+    if (!rate_io || !rate_io->S || !rate_io->uprev)
+        return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": rate_io, S and uprev are required");
+    if (staged && io->dQf)
+        return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": RQP_LTV_STAGE_WEIGHTS has no Qf, dQf must be NULL (the terminal "
+                                     "weight's gradient is the last stage of dQ)");
+    if (((dims->flags & RQP_LTV_HAS_K) && !io->K) || ((dims->flags & RQP_LTV_HAS_XREF) && !io->xref) ||
+        ((dims->flags & RQP_LTV_HAS_UREF) && !io->uref))
+        return ltv_fail(RQP_ERR_ARG, std::string(fn) + ": a flag names an input whose pointer is NULL");
+    if (rate_io->dA_r)
+        if (int rc = ltv_rate_stride(dims, rate_io->dA_stride, (int64_t)dims->horizon * dims->nu, fn)) return rc;
+    if (rate_io->dl_r || rate_io->du_r)
+        if (int rc = ltv_rate_stride(dims, rate_io->dl_stride, 1, fn)) return rc;
+    LtvDevice on;
+    if (int rc = on.enter(device, fn)) return rc;
+    hipError_t e = rqp_ltv_launch_condense_adjoint_rate(dims, io, rate_io, (hipStream_t)stream);
+    if (e != hipSuccess) return ltv_fail(RQP_ERR_HIP, std::string(fn) + ": " + hipGetErrorString(e));
+    return RQP_OK;
+}
+
 const char* rqp_last_error(const rqp_handle* h) { return h ? h->err.c_str() : ltv_err.c_str(); }
 
 const char* rqp_version(void) { return RQP_VERSION; }

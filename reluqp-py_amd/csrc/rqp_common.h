@@ -370,3 +370,18 @@ hipError_t rqp_ltv_launch_stage_adjoint(const rqp_ltv_dims* d, int nc, const rqp
 // reverse mode of the condensing (rqp_condense_adj.hip)
 size_t rqp_ltv_adj_ws_bytes(const rqp_ltv_dims* d);
 hipError_t rqp_ltv_launch_condense_adjoint(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io, hipStream_t s);
+void rqp_ltv_adj_ws_maps(const rqp_ltv_dims* d, void* aw, double** Fb, double** vec);   // Fb [B][m][n], vec [B][4][m] in the adjoint workspace
+// The same chain around the two kernels of the rate adjoint (rqp_rate.hip): `vectors` is launched in the place of k_ltva_vectors
+// (it writes what that kernel writes, never reading W), `rows` after k_ltva_blocks with need_fb = 1 when a sweep follows; when
+// neither the sweep nor the weight kernels run, `rows` is still launched (need_fb = 0) if rows_alone is set.
+struct rqp_ltv_adj_hooks {
+    void* ctx;
+    hipError_t (*vectors)(void* ctx, hipStream_t s);
+    hipError_t (*rows)(void* ctx, int need_fb, hipStream_t s);
+    bool rows_alone;
+};
+hipError_t rqp_ltv_launch_condense_adjoint_hooked(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io, const rqp_ltv_adj_hooks* hk,
+                                                  hipStream_t s);
+size_t rqp_ltv_rate_adj_ws_bytes(const rqp_ltv_dims* d);
+hipError_t rqp_ltv_launch_condense_adjoint_rate(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io,
+                                                const rqp_ltv_rate_adjoint_io* rio, hipStream_t s);

@@ -424,16 +424,23 @@ hipError_t launch_sweep(const LtvAdjArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
+// `hk` (rqp_ltv_condense_adjoint_rate, rqp_rate.hip): its vectors kernel runs in the place of k_ltva_vectors and its rows kernel
+// after k_ltva_blocks, before the sweep reads Fb.  NULL: the chain of rqp_ltv_condense_adjoint, launch by launch what it was.
 template <typename T, bool STAGED>
-hipError_t launch_adjoint_t(LtvAdjArgs& a, hipStream_t s) {
+hipError_t launch_adjoint_t(LtvAdjArgs& a, const rqp_ltv_adj_hooks* hk, hipStream_t s) {
     const int wsz = a.nu * a.nu + a.nx * a.nx;
     const bool sweep = a.dAd || a.dBd || a.dc, weights = a.dQ || a.dR || a.dQf;
     a.need_fb = sweep;
     a.need_w = weights;
     a.has_T = a.dH != nullptr;
-    k_ltva_vectors<T, STAGED><<<a.B, 256, sizeof(double) * (size_t)(a.nx + a.n + 2 * a.m + 256), s>>>(a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess || (!sweep && !weights)) return e;
+    hipError_t e;
+    if (hk) e = hk->vectors(hk->ctx, s);
+    else {
+        k_ltva_vectors<T, STAGED><<<a.B, 256, sizeof(double) * (size_t)(a.nx + a.n + 2 * a.m + 256), s>>>(a);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) return e;
+    if (!sweep && !weights) return (hk && hk->rows_alone) ? hk->rows(hk->ctx, 0, s) : e;
     if (a.has_T) {
         const int RTm = (a.m + 15) / 16, JP = ((a.n + 15) / 16 + 1) / 2;
         k_ltva_seed<T><<<(unsigned)((size_t)a.B * RTm * JP), 64, 0, s>>>(a, RTm, JP);
@@ -447,6 +454,7 @@ hipError_t launch_adjoint_t(LtvAdjArgs& a, hipStream_t s) {
     }
     k_ltva_blocks<T, STAGED><<<(unsigned)((size_t)a.B * a.N), 256, blds, s>>>(a, ld);
     if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (hk && (sweep || hk->rows_alone) && (e = hk->rows(hk->ctx, sweep ? 1 : 0, s)) != hipSuccess) return e;
     if (sweep) {
         switch (nxp_of(a.nx)) {
             case 4: e = launch_sweep<T, 4>(a, s); break;
@@ -477,7 +485,18 @@ size_t rqp_ltv_adj_ws_bytes(const rqp_ltv_dims* d) {
     return sizeof(double) * (B * (m * n + 4 * m + N * wsz) + (size_t)WSUM_SLICES * 2 * wsz);
 }
 
+void rqp_ltv_adj_ws_maps(const rqp_ltv_dims* d, void* aw, double** Fb, double** vec) {
+    const size_t B = d->batch, N = d->horizon;
+    *Fb = (double*)aw;
+    *vec = *Fb + B * (N * (d->nx + d->nu)) * (N * d->nu);
+}
+
 hipError_t rqp_ltv_launch_condense_adjoint(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io, hipStream_t s) {
+    return rqp_ltv_launch_condense_adjoint_hooked(d, io, nullptr, s);
+}
+
+hipError_t rqp_ltv_launch_condense_adjoint_hooked(const rqp_ltv_dims* d, const rqp_ltv_adjoint_io* io, const rqp_ltv_adj_hooks* hk,
+                                                  hipStream_t s) {
     LtvAdjArgs a;
     memset(&a, 0, sizeof(a));
     a.B = d->batch; a.nx = d->nx; a.nu = d->nu; a.N = d->horizon;
@@ -501,6 +520,6 @@ hipError_t rqp_ltv_launch_condense_adjoint(const rqp_ltv_dims* d, const rqp_ltv_
     a.wpart = a.vec + B * 4 * a.m;
     a.wsl = a.wpart + B * a.N * wsz;
     if (d->flags & RQP_LTV_STAGE_WEIGHTS)
-        return (d->dtype == RQP_F32) ? launch_adjoint_t<float, true>(a, s) : launch_adjoint_t<double, true>(a, s);
-    return (d->dtype == RQP_F32) ? launch_adjoint_t<float, false>(a, s) : launch_adjoint_t<double, false>(a, s);
+        return (d->dtype == RQP_F32) ? launch_adjoint_t<float, true>(a, hk, s) : launch_adjoint_t<double, true>(a, hk, s);
+    return (d->dtype == RQP_F32) ? launch_adjoint_t<float, false>(a, hk, s) : launch_adjoint_t<double, false>(a, hk, s);
 }

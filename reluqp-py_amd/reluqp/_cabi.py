@@ -27,7 +27,8 @@ ABI_SYMBOLS = (
     "rqp_get_state", "rqp_get_rhos", "rqp_get_K", "rqp_dispatch_history", "rqp_get_dispatch", "rqp_get_window", "rqp_set_window_passes", "rqp_set_polish", "rqp_get_polish", "rqp_set_adjoint", "rqp_adjoint", "rqp_set_sensitivity", "rqp_sensitivity",
     "rqp_ltv_workspace_bytes", "rqp_ltv_condense", "rqp_ltv_vectors", "rqp_ltv_adjoint_workspace_bytes",
     "rqp_ltv_condense_adjoint", "rqp_ltv_stage_rows", "rqp_ltv_stage_vectors", "rqp_ltv_stage_adjoint",
-    "rqp_ltv_condense_rate", "rqp_ltv_vectors_rate", "rqp_ltv_rate_rows", "rqp_ltv_rate_bounds", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
+    "rqp_ltv_condense_rate", "rqp_ltv_vectors_rate", "rqp_ltv_rate_rows", "rqp_ltv_rate_bounds",
+    "rqp_ltv_adjoint_rate_workspace_bytes", "rqp_ltv_condense_adjoint_rate", "rqp_kernel_name", "rqp_destroy", "rqp_strerror",
     "rqp_last_error", "rqp_version",
 )
 
@@ -94,6 +95,13 @@ class LtvAdjointIO(ctypes.Structure):
 class LtvStageAdjointIO(ctypes.Structure):
     """struct rqp_ltv_stage_adjoint_io: device pointers (None = NULL)."""
     _fields_ = [(f, ctypes.c_void_p) for f in ("E", "x0", "workspace", "dA_c", "dl_c", "du_c", "dA_full", "dl_full", "dE")]
+
+
+class LtvRateAdjointIO(ctypes.Structure):
+    """struct rqp_ltv_rate_adjoint_io: device pointers (None = NULL) and the two instance strides (elements)."""
+    _fields_ = ([(f, ctypes.c_void_p) for f in ("S", "uprev", "dA_r", "dl_r", "du_r")] +
+                [("dA_stride", ctypes.c_int64), ("dl_stride", ctypes.c_int64)] +
+                [(f, ctypes.c_void_p) for f in ("dS", "duprev")])
 
 
 class CInfo(ctypes.Structure):
@@ -163,6 +171,9 @@ def load():
         "rqp_ltv_vectors_rate": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 15),
         "rqp_ltv_rate_rows": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, vp, vp, ctypes.c_int64, vp]),
         "rqp_ltv_rate_bounds": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int] + [vp] * 7 + [ctypes.c_int64, vp]),
+        "rqp_ltv_adjoint_rate_workspace_bytes": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.POINTER(ctypes.c_size_t)]),
+        "rqp_ltv_condense_adjoint_rate": (ctypes.c_int, [ctypes.POINTER(LtvDims), ctypes.c_int, ctypes.POINTER(LtvAdjointIO),
+                                                         ctypes.POINTER(LtvRateAdjointIO), vp]),
         "rqp_kernel_name": (ctypes.c_char_p, [H]),
         "rqp_destroy": (ctypes.c_int, [H]),
         "rqp_strerror": (ctypes.c_char_p, [ctypes.c_int]),

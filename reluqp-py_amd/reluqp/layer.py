@@ -196,9 +196,11 @@ class LTVCondenseFunction(torch.autograd.Function):
         return slot, w
 
     @staticmethod
-    def reverse(ctx, gH, gA, gg, gl, gu, ninputs):
+    def reverse(ctx, gH, gA, gg, gl, gu, ninputs, rate=None):
         """The gradients of (Ad, Bd, c, x0, xref, uref, Q, R, Qf) -- inputs 1 .. 9 of ``forward`` -- that ``needs_input_grad``
-        names, in a list of ``ninputs`` entries (the others None)."""
+        names, in a list of ``ninputs`` entries (the others None).  ``rate`` (``LTVRateFunction``): the keyword arguments of
+        ``mpc.condense_ltv_adjoint_rate_device`` beside the cotangents above, and ``want``, which of "S", "uprev" to compute
+        as well; those two come back in ``rate["out"]``."""
         Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd = ctx.saved_tensors[:9]
         names = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
         want = tuple(k for k, nd in zip(names, ctx.needs_input_grad[1:10]) if nd)
@@ -206,10 +208,17 @@ class LTVCondenseFunction(torch.autograd.Function):
         if staged and "Qf" in want:                                      # (a shared Q beside a staged R: Qf is stage N-1 of Q)
             want = tuple(k for k in want if k not in ("Q", "Qf")) + ("Q",)
         grads = [None] * ninputs
-        if want:
+        extra = () if rate is None else tuple(rate["want"])
+        if want or extra:
             slot, w = LTVCondenseFunction.restore(ctx)
-            out = mpc.condense_ltv_adjoint_device(Ad, Bd, x0, w, slot["ws"], slot["adj"], xref=xref, uref=uref, dH=gH, dA=gA,
-                                                  dg=gg, dl=gl, du=gu, want=want)
+            if rate is None:
+                out = mpc.condense_ltv_adjoint_device(Ad, Bd, x0, w, slot["ws"], slot["adj"], xref=xref, uref=uref, dH=gH, dA=gA,
+                                                      dg=gg, dl=gl, du=gu, want=want)
+            else:
+                out = mpc.condense_ltv_adjoint_rate_device(Ad, Bd, x0, w, slot["ws"], ctx.condenser.rate_adjoint_workspace(slot),
+                                                           xref=xref, uref=uref, dH=gH, dA=gA, dg=gg, dl=gl, du=gu,
+                                                           want=want + extra, **{k: v for k, v in rate.items() if k != "want"})
+                rate["out"] = {k: out.pop(k) for k in extra}
             if staged:                                                   # [B, N, ., .] back to the shape the weight was given in
                 N = Ad.shape[1]
                 if "Q" in out and ctx.wdims[0] == 2:
@@ -292,6 +301,106 @@ class StageConstraintFunction(torch.autograd.Function):
         return tuple(grads)
 
 
+class LTVRateFunction(torch.autograd.Function):
+    """``LTVRateFunction.apply(condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, b0, b1, b2, S, u_prev, du_lo, du_hi)`` ->
+    ``(H, A, g, l, u)``: the condensed QPs with input rates (DESIGN.md section 5 "LTV condensing, input rates").  The base rows
+    are the box (b0 = None, b1, b2 = l_add, u_add) or stage rows (b0, b1, b2 = E, lo, hi).  S [nu, nu], [N, nu, nu] or
+    [B, N, nu, nu] is the rate weight (None: no rate cost, S = 0 on the same kernels), u_prev [B, nu] the input applied before
+    stage 0; du_lo, du_hi [N nu] or [B, N nu] (both or neither) append the N nu slew-rate rows after the base rows, as
+    ``mpc.BatchedLTVMPC`` places them.  Forward: C-ABI rqp_ltv_condense_rate + rqp_ltv_vectors_rate (+ rqp_ltv_stage_rows /
+    rqp_ltv_stage_vectors, rqp_ltv_rate_rows / rqp_ltv_rate_bounds).  Backward: rqp_ltv_condense_adjoint_rate (after
+    rqp_ltv_stage_adjoint for stage rows), which reads the tails of the cotangents of (A, l, u) in place; it shares
+    ``LTVCondenseFunction``'s workspace stamp (only F and [G | f] of the workspace are read, so a re-condense needs no S).
+    Gradients of S, du_lo, du_hi come back in the input's shape, summed where the input is shared."""
+
+    @staticmethod
+    def forward(ctx, condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, b0, b1, b2, S, u_prev, du_lo, du_hi):
+        cd = condenser
+        dtype, device, B = Ad.dtype, Ad.device, Ad.shape[0]
+        nx, nu, N, n = cd.nx, cd.nu, cd.horizon, cd.n
+        slot = cd.slot(B, device, dtype)
+        w, (Qd, Rd, Qfd) = _ltv_layer_weights(cd, slot, B, device, Q, R, Qf)
+        det = lambda t: None if t is None else t.detach().contiguous()
+        Ad, Bd, c, x0, xref, uref = (det(t) for t in (Ad, Bd, c, x0, xref, uref))
+        stage, rows = b0 is not None, du_lo is not None
+        Ed = b0.detach().to(device=device, dtype=dtype).contiguous() if stage else None
+        Sd = mpc.rate_weight_device(torch.zeros(nu, nu, dtype=torch.float64, device=device) if S is None else S, nu, N, B, device)
+        up = u_prev.detach().to(device=device, dtype=dtype).contiguous()
+        slot["stamp"] = ctx.stamp = cd.next_stamp()
+        dims4, dims5 = (B, nx, nu, N), (nx, nu, N, cd.K is not None, c is not None)
+        m0 = N * Ed.shape[-2] if stage else cd.m
+        if stage:
+            _, As = cd.recondense_outputs(slot, B, device, dtype)        # (A = F of the box is not an output here)
+            H, _ = mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, A=As, S=Sd)
+            if "box0" not in slot:
+                slot["box0"] = torch.zeros(cd.m, dtype=dtype, device=device)
+            g, _, _ = mpc.ltv_vectors_device(dims5, x0, slot["box0"], slot["box0"], w, slot["ws"], xref=xref, uref=uref, S=Sd, uprev=up)
+            A0 = mpc.stage_rows_device(dims4, Ed, slot["ws"])
+            l0, u0 = mpc.stage_vectors_device(dims4, Ed, x0, b1.detach(), b2.detach(), slot["ws"])
+        else:
+            H, A0 = mpc.condense_ltv_device(Ad, Bd, w, slot["ws"], c=c, S=Sd)
+            g, l0, u0 = mpc.ltv_vectors_device(dims5, x0, b1.detach(), b2.detach(), w, slot["ws"], xref=xref, uref=uref, S=Sd, uprev=up)
+        if rows:
+            A = torch.empty((B, m0 + n, n), dtype=dtype, device=device)
+            l, u = torch.empty((B, m0 + n), dtype=dtype, device=device), torch.empty((B, m0 + n), dtype=dtype, device=device)
+            A[:, :m0].copy_(A0)
+            l[:, :m0].copy_(l0)
+            u[:, :m0].copy_(u0)
+            mpc.rate_rows_device(dims4, slot["ws"], dtype, A_r=A, row0=m0)
+            mpc.rate_bounds_device(dims4, x0, up, du_lo.detach(), du_hi.detach(), slot["ws"], l_r=l, u_r=u, row0=m0)
+        else:
+            A, l, u = A0, l0, u0
+        ctx.condenser, ctx.slot, ctx.dims4, ctx.m0, ctx.stage, ctx.rows = cd, slot, dims4, m0, stage, rows
+        ctx.meta = (Q.dtype, R.dtype, None if Qf is None else Qf.dtype)
+        ctx.wdims = (Q.dim(), R.dim())
+        ctx.like = [None if t is None else (t.dim(), t.dtype) for t in (b0, b1, b2, S, u_prev, du_lo, du_hi)]
+        ctx.save_for_backward(Ad, Bd, c, x0, xref, uref, Qd, Rd, Qfd, Ed, Sd, up)
+        ctx.set_materialize_grads(False)
+        return H, A, g, l, u
+
+    @staticmethod
+    def backward(ctx, gH, gA, gg, gl, gu):
+        need, m0, like = ctx.needs_input_grad, ctx.m0, ctx.like
+        x0, Ed, Sd, up = ctx.saved_tensors[3], ctx.saved_tensors[9], ctx.saved_tensors[10], ctx.saved_tensors[11]
+        con = lambda t: None if t is None else t.contiguous()
+        gA, gl, gu = con(gA), con(gl), con(gu)
+        head = lambda t: t if (t is None or not ctx.rows) else t[:, :m0].contiguous()
+        dA, dl, du = head(gA), head(gl), head(gu)
+        plant = any(need[1:10])
+        dE = None
+        if ctx.stage:
+            dA_c, dl_c, du_c = dA, dl, du
+            dA = dl = du = None
+            if (dA_c is not None or dl_c is not None or du_c is not None) and (plant or need[10]):
+                slot, _ = LTVCondenseFunction.restore(ctx)
+                want = (("dA_full", "dl_full") if plant else ()) + (("dE",) if need[10] else ())
+                out = mpc.stage_adjoint_device(ctx.dims4, Ed, x0, slot["ws"], dA_c=dA_c, dl_c=dl_c, du_c=du_c, want=want)
+                dA, dl, dE = out.get("dA_full"), out.get("dl_full"), out.get("dE")
+        else:
+            dl_c, du_c = dl, du
+        rows = ctx.rows
+        rate = dict(S=Sd, uprev=up, row0=m0 if rows else 0, dA_r=gA if rows else None, dl_r=gl if rows else None,
+                    du_r=gu if rows else None, want=(("S",) if need[13] else ()) + (("uprev",) if need[14] else ()))
+        grads = LTVCondenseFunction.reverse(ctx, gH, dA, gg, dl, du, 17, rate=rate)
+        out = rate.get("out", {})
+        if dE is not None:
+            grads[10] = (dE if like[0][0] == 4 else dE.sum(0)).to(like[0][1])
+        for i, gb in ((11, dl_c), (12, du_c)):                           # the base bounds: l_add, u_add or lo, hi
+            if need[i] and gb is not None:
+                grads[i] = (gb if like[i - 10][0] == 2 else gb.sum(0)).to(like[i - 10][1])
+        if "S" in out:                                                   # [B, N, nu, nu] back to the shape S was given in
+            dS = out["S"]
+            dS = dS if like[3][0] == 4 else (dS.sum(0) if like[3][0] == 3 else dS.sum((0, 1)))
+            grads[13] = dS.to(like[3][1])
+        if "uprev" in out:
+            grads[14] = out["uprev"].to(like[4][1])
+        for i, gb in ((15, gl), (16, gu)):
+            if rows and need[i] and gb is not None:
+                tail = gb[:, m0:]
+                grads[i] = (tail if like[i - 10][0] == 2 else tail.sum(0)).to(like[i - 10][1])
+        return tuple(grads)
+
+
 class LTVMPCLayer(torch.nn.Module):
     """Differentiable MPC on a batch of LTV plants: ``u0, v = LTVMPCLayer(nx, nu, horizon, u_max, x_max, K=None)(Ad, Bd, x0, Q, R,
     Qf, c=None, xref=None, uref=None)``.  The stages are condensed on the device (``LTVCondenseFunction``), the QPs solved by a
@@ -307,9 +416,17 @@ class LTVMPCLayer(torch.nn.Module):
     ``LTVMPCLayer(nx, nu, horizon, K=None, stage_rows=nc)`` (no u_max, x_max) replaces the box by nc rows per stage, lo_k <=
     E_k [u_k ; x_{k+1}] <= hi_k, given with every call: ``layer(Ad, Bd, x0, Q, R, Qf, ..., E=, lo=, hi=)`` with E [B, N, nc,
     nu + nx] or shared [N, nc, nu + nx] and lo, hi [B, N nc] or [N nc] (``StageConstraintFunction``).  Gradients then also flow
-    to E, lo and hi (summed over the batch where the input is shared)."""
+    to E, lo and hi (summed over the batch where the input is shared).
 
-    def __init__(self, nx, nu, horizon, u_max=None, x_max=None, K=None, stage_rows=None, **setup_kwargs):
+    Input rates (``LTVRateFunction``; both act on the plant's input u_k = -K x_k + v_k): ``layer(..., S=, u_prev=)`` adds the
+    move-suppression cost 1/2 sum_k (u_k - u_{k-1})' S_k (u_k - u_{k-1}), u_{-1} = u_prev [B, nu], with S [nu, nu], [N, nu, nu]
+    or [B, N, nu, nu] (symmetric blocks); ``LTVMPCLayer(..., rate_rows=True)`` appends the N nu rows du_lo_k <= u_k - u_{k-1} <=
+    du_hi_k after the box or the stage rows, their bounds given with every call: ``layer(..., u_prev=, du_lo=, du_hi=)``, [N nu]
+    or [B, N nu].  The cost alone, the rows alone, or both.  Gradients then also flow to S, u_prev, du_lo and du_hi, in the
+    input's shape (summed over the batch, and for S [nu, nu] over the stages, where the input is shared).  Without any rate
+    argument the layer makes the calls it made before."""
+
+    def __init__(self, nx, nu, horizon, u_max=None, x_max=None, K=None, stage_rows=None, rate_rows=False, **setup_kwargs):
         super().__init__()
         self.condenser = mpc.LTVCondenser(nx, nu, horizon, K=K)
         self.nx, self.nu, self.horizon = self.condenser.nx, self.condenser.nu, self.condenser.horizon
@@ -323,6 +440,11 @@ class LTVMPCLayer(torch.nn.Module):
             if u_max is None or x_max is None:
                 raise ValueError("u_max and x_max are required without stage_rows")
             _, self.l_add, self.u_add = mpc.box_constraints(self.nx, self.nu, self.horizon, u_max, x_max)
+        self.rate_rows = bool(rate_rows)
+        m0 = self.horizon * (self.stage_rows if self.stage_rows is not None else self.nx + self.nu)
+        if self.rate_rows and m0 + self.horizon * self.nu > mpc.LTV_LIMITS["m"]:
+            raise ValueError("unsupported size: %d base rows + %d rate rows, the QPs hold m <= %d"
+                             % (m0, self.horizon * self.nu, mpc.LTV_LIMITS["m"]))
         self.qp = ReLUQPLayer(**setup_kwargs)
         self._const = {}
 
@@ -347,7 +469,39 @@ class LTVMPCLayer(torch.nn.Module):
         if any(t.device != device for t in (E, lo, hi)):
             raise ValueError("E, lo, hi must be on the device of Ad (%s)" % device)
 
-    def _check(self, Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(None, None, None)):
+    def _check_rate(self, B, dtype, device, S, u_prev, du_lo, du_hi):
+        """True when the call has rate terms.  (The symmetry of S is tested in ``_check``, in the read-back it makes for Q, R, Qf.)"""
+        nu, N = self.nu, self.horizon
+        if not self.rate_rows and (du_lo is not None or du_hi is not None):
+            raise ValueError("du_lo, du_hi need LTVMPCLayer(rate_rows=True)")
+        if self.rate_rows and (du_lo is None or du_hi is None):
+            raise ValueError("rate_rows: du_lo and du_hi must be given")
+        if S is None and not self.rate_rows:
+            if u_prev is not None:
+                raise ValueError("u_prev needs S or LTVMPCLayer(rate_rows=True)")
+            return False
+        if u_prev is None:
+            raise ValueError("input rates need u_prev [B, nu], the input applied before stage 0")
+        for name, t in (("S", S), ("u_prev", u_prev), ("du_lo", du_lo), ("du_hi", du_hi)):
+            if t is not None and not torch.is_tensor(t):
+                raise ValueError("%s must be given as a torch tensor" % name)
+        if S is not None:
+            mpc._rate_weight_shapes(nu, N, S, B=B)
+        if tuple(u_prev.shape) != (B, nu):
+            raise ValueError("u_prev has shape %s, expected %s" % (tuple(u_prev.shape), (B, nu)))
+        if self.rate_rows:
+            for name, t in (("du_lo", du_lo), ("du_hi", du_hi)):
+                if tuple(t.shape) not in ((B, N * nu), (N * nu,)):
+                    raise ValueError("%s has shape %s, expected %s or %s" % (name, tuple(t.shape), (B, N * nu), (N * nu,)))
+            if du_lo.dim() != du_hi.dim():
+                raise ValueError("du_lo and du_hi must both be [B, N nu] or both [N nu]")
+        if any(t is not None and t.dtype != dtype for t in (u_prev, du_lo, du_hi)):
+            raise ValueError("u_prev, du_lo, du_hi must have the precision of Ad")
+        if any(t is not None and t.device != device for t in (S, u_prev, du_lo, du_hi)):
+            raise ValueError("S, u_prev, du_lo, du_hi must be on the device of Ad (%s)" % device)
+        return True
+
+    def _check(self, Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(None, None, None), rate=(None, None, None, None)):
         nx, nu, N = self.nx, self.nu, self.horizon
         staged = torch.is_tensor(Q) and torch.is_tensor(R) and (Q.dim() > 2 or R.dim() > 2)
         for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("Q", Q), ("R", R)) + (() if staged and Qf is None else (("Qf", Qf),)):
@@ -364,8 +518,11 @@ class LTVMPCLayer(torch.nn.Module):
         elif tuple(Q.shape) != (nx, nx) or tuple(Qf.shape) != (nx, nx) or tuple(R.shape) != (nu, nu):
             raise ValueError("Q, Qf must be [%d, %d] and R [%d, %d]" % (nx, nx, nu, nu))
         # symmetric up to rounding, as BatchedLTVMPC asks (the symmetric part is what is used); the three tests share one read-back
+        # (a rate weight S on the device of Q joins them: no read-back of its own)
         sym = [(name, W) for name, W in (("Q", Q), ("R", R), ("Qf", Qf)) if W is not None]
-        asym = torch.stack([(W.detach() - W.detach().transpose(-1, -2)).abs().max() - 1e-9 * W.detach().abs().max()
+        if torch.is_tensor(rate[0]) and rate[0].dim() >= 2 and rate[0].device == Q.device:
+            sym.append(("S", rate[0]))
+        asym = torch.stack([((W.detach() - W.detach().transpose(-1, -2)).abs().max() - 1e-9 * W.detach().abs().max()).double()
                             for _, W in sym]).tolist()
         for (name, _), a in zip(sym, asym):
             if a > 0:
@@ -373,18 +530,23 @@ class LTVMPCLayer(torch.nn.Module):
         if Ad.dtype not in (torch.float32, torch.float64) or any(t is not None and t.dtype != Ad.dtype for t in (Bd, x0, c, xref, uref)):
             raise ValueError("Ad, Bd, x0 (c, xref, uref) must share one precision, float32 or float64")
         self._check_stage(B, Ad.dtype, Ad.device, *stage)
+        has_rate = self._check_rate(B, Ad.dtype, Ad.device, *rate)
         if Ad.device.type != "cuda":
             raise _cabi.RqpUnavailable("LTVMPCLayer needs a HIP device; the MI355X build has no CPU path")
-        return B
+        return B, has_rate
 
-    def forward(self, Ad, Bd, x0, Q, R, Qf, c=None, xref=None, uref=None, E=None, lo=None, hi=None):
-        B = self._check(Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(E, lo, hi))
+    def forward(self, Ad, Bd, x0, Q, R, Qf, c=None, xref=None, uref=None, E=None, lo=None, hi=None, S=None, u_prev=None, du_lo=None,
+                du_hi=None):
+        B, has_rate = self._check(Ad, Bd, x0, Q, R, Qf, c, xref, uref, stage=(E, lo, hi), rate=(S, u_prev, du_lo, du_hi))
         key = (str(Ad.device), Ad.dtype)
         if key not in self._const:
             t = lambda a: None if a is None else torch.as_tensor(a, dtype=Ad.dtype, device=Ad.device)
             self._const[key] = (t(self.l_add), t(self.u_add), t(self.condenser.K))
         l_add, u_add, K = self._const[key]
-        if self.stage_rows is None:
+        if has_rate:
+            base = (None, l_add, u_add) if self.stage_rows is None else (E, lo, hi)
+            H, A, g, l, u = LTVRateFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, *base, S, u_prev, du_lo, du_hi)
+        elif self.stage_rows is None:
             H, A, g, l, u = LTVCondenseFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, l_add, u_add)
         else:
             H, A, g, l, u = StageConstraintFunction.apply(self.condenser, Ad, Bd, c, x0, xref, uref, Q, R, Qf, E, lo, hi)

@@ -588,7 +588,7 @@ _LTV_VJP_KEYS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf", "l_add",
 
 
 def condense_ltv_vjp(Ad, Bd, Q, R, Qf=None, x0=None, l_add=None, u_add=None, K=None, c=None, xref=None, uref=None,
-                     dH=None, dA=None, dg=None, dl=None, du=None):
+                     dH=None, dA=None, dg=None, dl=None, du=None, S=None, uprev=None, dA_r=None, dl_r=None, du_r=None):
     """Reverse of ``condense_ltv`` + ``ltv_vectors`` on the host (numpy): the cotangents dH [n, n], dA [m, n], dg [n],
     dl, du [m] of (H, A, g, l, u) (an absent one is zero) mapped back to the inputs.  One instance, or a leading batch axis
     on Ad, Bd (and on c, x0, xref, uref, the cotangents, and l_add / u_add when they are [B, m]).  Returns a dict with the
@@ -604,9 +604,23 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf=None, x0=None, l_add=None, u_add=None, K=N
         Sb = F T' + (F dg) e' (its diagonal blocks give Rb, Qb, Qfb),
     and the reverse sweep over the stages, Lam = the x_N rows of Yb = [Fb | Gb | fb], X_k = the x_k rows of [F | G | f]:
         k = N-1 .. 0:  Aclb = Lam X_k',  Adb_k = Aclb,  Bdb_k = Lam[:, k nu:(k+1) nu] - Aclb K',  cb_k = Lam[:, f],
-                       Lam <- Acl_k' Lam - K' Yb[u_k rows] + Yb[x_k rows]   (k >= 1)."""
+                       Lam <- Acl_k' Lam - K' Yb[u_k rows] + Yb[x_k rows]   (k >= 1).
+
+    Input rates (any of ``S``, ``uprev``, ``dA_r``, ``dl_r``, ``du_r`` given): the reverse of ``condense_ltv(S=)`` +
+    ``ltv_vectors(uprev=)`` + ``rate_constraints``, written by the definitions with a dense D = ``_rate_difference``.  dH, dg are
+    then the cotangents of the rate problem's H, g; dA_r [N nu, n], dl_r, du_r [N nu] those of (A_r, l_r, u_r); S [nu, nu],
+    [N, nu, nu] or [B, N, nu, nu] (absent: zero, the rows alone), uprev [nu] ([B, nu]; absent: zero).  With Sig = blkdiag(S_k),
+    a = [uprev; 0; ...], dF = D F, r = D s - a, q = D F dg, t = dl_r + du_r, M = dF Hs, Z = dA_r + Sig (2 M + r dg'):
+        dA + D'Z in the place of dA,   dl + D'(t - Sig q) in the place of dl   (the gradient of l_add stays dl),
+        Sb_k = sym(M_k dF_k' + q_k r_k'),   uprevb = t_0 - S_0 q_0,   dlob = dl_r,   dhib = du_r,
+    and the dict gains S (in the shape S was given: summed over the stages for [nu, nu], over the batch without a batch axis),
+    uprev, dlo, dhi (per instance)."""
     Ad, Bd = np.asarray(Ad), np.asarray(Bd)
     Q, R = np.asarray(Q), np.asarray(R)
+    rate = any(v is not None for v in (S, uprev, dA_r, dl_r, du_r))
+    if rate:
+        S = np.zeros((Bd.shape[-1], Bd.shape[-1])) if S is None else np.asarray(S)
+        _rate_weight_shapes(Bd.shape[-1], Ad.shape[-3], S, B=Ad.shape[0] if Ad.ndim == 4 else None)
     if Ad.ndim == 4:
         B = Ad.shape[0]
         at = lambda a, b: None if a is None else np.asarray(a)[b]
@@ -616,8 +630,13 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf=None, x0=None, l_add=None, u_add=None, K=N
             _ltv_stage_shapes(Ad.shape[2], Bd.shape[3], Ad.shape[1], Q, R, Qf if Qf is None else np.asarray(Qf), B=B)
         outs = [condense_ltv_vjp(Ad[b], Bd[b], wt(Q, b), wt(R, b), Qf, np.asarray(x0)[b], lu(l_add, b), lu(u_add, b), K=K,
                                  c=at(c, b), xref=at(xref, b), uref=at(uref, b), dH=at(dH, b), dA=at(dA, b), dg=at(dg, b),
-                                 dl=at(dl, b), du=at(du, b)) for b in range(B)]
+                                 dl=at(dl, b), du=at(du, b), S=wt(S, b) if rate else None, uprev=at(uprev, b), dA_r=at(dA_r, b),
+                                 dl_r=at(dl_r, b), du_r=at(du_r, b)) for b in range(B)]
         res = {}
+        if rate:
+            res["S"] = np.stack([o["S"] for o in outs])
+            res["S"] = res["S"] if S.ndim == 4 else res["S"].sum(0)
+            res.update({k: np.stack([o[k] for o in outs]) for k in ("uprev", "dlo", "dhi")})
         for k in _LTV_VJP_KEYS:
             if k not in outs[0]:                               # (staged Q: no Qf)
                 continue
@@ -636,12 +655,28 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf=None, x0=None, l_add=None, u_add=None, K=N
     Hb, Ab, gb, lb, ub = cast(dH, (n, n)), cast(dA, (m, n)), cast(dg, (n,)), cast(dl, (m,)), cast(du, (m,))
     cond = condense_ltv(Ad, Bd, Q.astype(dt), R.astype(dt), None if Qf is None else np.asarray(Qf).astype(dt), K=Kz,
                         c=None if c is None else np.asarray(c).astype(dt))
-    F, G, f, S = cond["F"], cond["G"], cond["f"], cond["H_sp"]
+    F, G, f, S_sp = cond["F"], cond["G"], cond["f"], cond["H_sp"]
     e = G @ x0 + f - np.hstack([uref, xref]).reshape(-1)
     Hs = (Hb + Hb.T) / 2
     T = F @ Hs
-    Fb = Ab + 2 * (S @ T) + np.outer(S @ e, gb)
-    eb = S @ (F @ gb)
+    rate_out, lb_in = {}, lb
+    if rate:
+        Sr = S.astype(dt)
+        Sk = np.stack([Sr] * N) if Sr.ndim == 2 else Sr
+        D, Sig = _rate_difference(N, nx, nu, dt), _blkdiag_dense(Sk)
+        a0 = np.zeros(n, dtype=dt)
+        a0[:nu] = cast(uprev, (nu,))
+        Arb, lrb, urb = cast(dA_r, (n, n)), cast(dl_r, (n,)), cast(du_r, (n,))
+        dF, r, q, t = D @ F, D @ (G @ x0 + f) - a0, D @ (F @ gb), lrb + urb
+        M = dF @ Hs
+        Ab = Ab + D.T @ (Arb + Sig @ (2 * M + np.outer(r, gb)))
+        lb = lb + D.T @ (t - Sig @ q)
+        Sb = np.stack([M[k * nu:(k + 1) * nu] @ dF[k * nu:(k + 1) * nu].T + np.outer(q[k * nu:(k + 1) * nu], r[k * nu:(k + 1) * nu])
+                       for k in range(N)])
+        Sb = (Sb + np.swapaxes(Sb, 1, 2)) / 2
+        rate_out = dict(S=Sb.sum(0) if Sr.ndim == 2 else Sb, uprev=t[:nu] - Sk[0] @ q[:nu], dlo=lrb, dhi=urb)
+    Fb = Ab + 2 * (S_sp @ T) + np.outer(S_sp @ e, gb)
+    eb = S_sp @ (F @ gb)
     sb = eb - lb - ub
     Yb = np.hstack([Fb, np.outer(sb, x0), sb[:, None]])
     Fg = F @ gb
@@ -677,8 +712,8 @@ def condense_ltv_vjp(Ad, Bd, Q, R, Qf=None, x0=None, l_add=None, u_add=None, K=N
         if k >= 1:
             Lam = (Ad[k] - Bd[k] @ Kz).T @ Lam - Kz.T @ Yu + Yb[(k - 1) * blk + nu:k * blk]
     yr = (-eb).reshape(N, blk)
-    return dict(Ad=Adb, Bd=Bdb, c=cb, x0=G.T @ sb, xref=yr[:, nu:].copy(), uref=yr[:, :nu].copy(), l_add=lb, u_add=ub, K=Kb,
-                **weights)
+    return dict(Ad=Adb, Bd=Bdb, c=cb, x0=G.T @ sb, xref=yr[:, nu:].copy(), uref=yr[:, :nu].copy(), l_add=lb_in, u_add=ub, K=Kb,
+                **weights, **rate_out)
 
 
 # Stage constraints: instead of the box on y, stage k carries nc rows  lo_k <= E_k [u_k ; x_{k+1}] <= hi_k  (m_c = N nc rows).
@@ -862,7 +897,37 @@ def ltv_adjoint_workspace(batch, nx, nu, horizon, device):
     return torch.empty(nbytes.value // 8, dtype=torch.float64, device=device)
 
 
+def ltv_adjoint_rate_workspace(batch, nx, nu, horizon, device):
+    """The float64 workspace of ``condense_ltv_adjoint_rate_device`` for these sizes (a device tensor): that of
+    ``ltv_adjoint_workspace`` and 2 N nu doubles per instance; it serves ``condense_ltv_adjoint_device`` as well."""
+    import ctypes
+    import torch
+    from reluqp import _cabi
+    _ltv_check_sizes(nx, nu, horizon)
+    lib = _cabi.load()
+    dims = _cabi.LtvDims(batch=batch, nx=nx, nu=nu, horizon=horizon, dtype=_cabi.RQP_F64, flags=0)
+    nbytes = ctypes.c_size_t()
+    _cabi.check(None, lib.rqp_ltv_adjoint_rate_workspace_bytes(ctypes.byref(dims), ctypes.byref(nbytes)),
+                "rqp_ltv_adjoint_rate_workspace_bytes", handleless=True)
+    return torch.empty(nbytes.value // 8, dtype=torch.float64, device=device)
+
+
 LTV_ADJOINT_OUTPUTS = ("Ad", "Bd", "c", "x0", "xref", "uref", "Q", "R", "Qf")
+LTV_RATE_ADJOINT_OUTPUTS = LTV_ADJOINT_OUTPUTS + ("S", "uprev")
+
+
+def condense_ltv_adjoint_rate_device(Ad, Bd, x0, weights, workspace, adjoint_workspace, S, uprev, xref=None, uref=None, dH=None,
+                                     dA=None, dg=None, dl=None, du=None, dA_r=None, dl_r=None, du_r=None, row0=0, want=None):
+    """Reverse of ``condense_ltv_device(S=)`` + ``ltv_vectors_device(S=, uprev=)`` + ``rate_rows_device`` +
+    ``rate_bounds_device`` on the device (C-ABI rqp_ltv_condense_adjoint_rate; the host statement is ``condense_ltv_vjp`` with
+    its rate keywords).  As ``condense_ltv_adjoint_device``, and: ``S`` from ``rate_weight_device``, ``uprev`` [B, nu];
+    ``workspace`` from either way of condensing this linearisation; ``adjoint_workspace`` from ``ltv_adjoint_rate_workspace``;
+    dH, dg the cotangents of the rate problem's H, g; dA, dl, du those of the base rows; dA_r [B, mt, n], dl_r, du_r [B, mt] those
+    of the rate rows, which are rows row0 .. row0 + N nu of every instance (mt = N nu and row0 = 0: the rate rows alone; else
+    the tails of the whole QP's cotangents, read in place).  ``want`` may also name "S" ([B, N, nu, nu] float64, per instance
+    and stage) and "uprev" ([B, nu])."""
+    return _ltv_adjoint_call(Ad, Bd, x0, weights, workspace, adjoint_workspace, xref, uref, dH, dA, dg, dl, du, want,
+                             rate=dict(S=S, uprev=uprev, dA_r=dA_r, dl_r=dl_r, du_r=du_r, row0=int(row0)))
 
 
 def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspace, xref=None, uref=None, dH=None, dA=None,
@@ -874,21 +939,28 @@ def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspac
     precision; Q, R, Qf float64, summed over the batch).  Stage weights (``_LtvStageWeights``, or staged Q, R in the tuple): Q, R
     come back [B, N, ., .] float64, each block its own instance's and stage's, and "Qf" cannot be wanted.  Enqueued on the
     current stream."""
+    return _ltv_adjoint_call(Ad, Bd, x0, weights, workspace, adjoint_workspace, xref, uref, dH, dA, dg, dl, du, want)
+
+
+def _ltv_adjoint_call(Ad, Bd, x0, weights, workspace, adjoint_workspace, xref, uref, dH, dA, dg, dl, du, want, rate=None):
+    """The two device adjoints: ``rate`` None is rqp_ltv_condense_adjoint, else rqp_ltv_condense_adjoint_rate."""
     import ctypes
     import torch
     from reluqp import _cabi
     B, N, nx, nu = _ltv_shapes(Ad, Bd)
     _ltv_check_sizes(nx, nu, N)
     if not torch.is_tensor(Ad) or Ad.device.type != "cuda":
-        raise _cabi.RqpUnavailable("condense_ltv_adjoint_device needs device tensors; the host restatement is condense_ltv_vjp")
+        raise _cabi.RqpUnavailable("condense_ltv_adjoint%s_device needs device tensors; the host restatement is condense_ltv_vjp"
+                                   % ("" if rate is None else "_rate"))
     dtype, device = Ad.dtype, Ad.device
     n, m = N * nu, N * (nx + nu)
     Q, R, Qf, K, staged = _ltv_weights_on(weights, nx, nu, N, B, device)
+    known = LTV_ADJOINT_OUTPUTS if rate is None else LTV_RATE_ADJOINT_OUTPUTS
     if want is None:                           # every gradient there is
-        want = tuple(k for k in LTV_ADJOINT_OUTPUTS if not (staged and k == "Qf"))
-    unknown = [k for k in want if k not in LTV_ADJOINT_OUTPUTS]
+        want = tuple(k for k in known if not (staged and k == "Qf"))
+    unknown = [k for k in want if k not in known]
     if unknown:
-        raise ValueError("unknown gradient name(s) %s; known: %s" % (unknown, LTV_ADJOINT_OUTPUTS))
+        raise ValueError("unknown gradient name(s) %s; known: %s" % (unknown, known))
     if staged and "Qf" in want:
         raise ValueError("stage weights have no Qf: its gradient is that of Q[:, N-1]")
     opt = lambda t, shape, name: None if t is None else _ltv_in(t, shape, dtype, device, name)
@@ -900,14 +972,39 @@ def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspac
                   Q=(nx, nx), R=(nu, nu), Qf=(nx, nx))
     if staged:
         shapes.update(Q=(B, N, nx, nx), R=(B, N, nu, nu))
-    out = {k: torch.empty(shapes[k], dtype=torch.float64 if k in ("Q", "R", "Qf") else dtype, device=device) for k in want}
+    shapes.update(S=(B, N, nu, nu), uprev=(B, nu))
+    out = {k: torch.empty(shapes[k], dtype=torch.float64 if k in ("Q", "R", "Qf", "S") else dtype, device=device) for k in want}
+    rio = None
+    if rate is not None:
+        rio, row0 = _cabi.LtvRateAdjointIO(), rate["row0"]
+        rio.S = _rate_tensor(rate["S"], (B, N, nu, nu), device).data_ptr()
+        rio.uprev = _ltv_in(rate["uprev"], (B, nu), dtype, device, "uprev").data_ptr()
+        keep = []                              # (the tensors whose addresses rio holds stay alive until the call)
+        for name, row in (("dA_r", (n,)), ("dl_r", ()), ("du_r", ())):
+            t = rate[name]
+            if t is None:
+                continue
+            t = torch.as_tensor(t).to(device=device, dtype=dtype).contiguous()
+            if t.dim() != 2 + len(row) or t.shape[0] != B or tuple(t.shape[2:]) != row or row0 < 0 or row0 + n > t.shape[1]:
+                raise ValueError("%s has shape %s, expected [%d, mt%s] with the %d rate rows from row %d on"
+                                 % (name, tuple(t.shape), B, ", %d" % n if row else "", n, row0))
+            keep.append(t)
+            per_row = n if row else 1
+            setattr(rio, name, t.data_ptr() + row0 * per_row * t.element_size())
+            setattr(rio, "dA_stride" if row else "dl_stride", t.shape[1] * per_row)
+        if rate["dl_r"] is not None and rate["du_r"] is not None and rate["dl_r"].shape[1] != rate["du_r"].shape[1]:
+            raise ValueError("dl_r and du_r must have the same shape")
+        for k in ("S", "uprev"):
+            if k in out:
+                setattr(rio, "d" + k, out[k].data_ptr())
     io = _cabi.LtvAdjointIO()
     for name, t in (("Ad", Ad), ("Bd", Bd), ("x0", x0), ("xref", xref), ("uref", uref), ("Q", Q), ("R", R), ("Qf", Qf), ("K", K),
                     ("workspace", workspace), ("dH", dH), ("dA", dA), ("dg", dg), ("dl", dl), ("du", du),
                     ("adjoint_workspace", adjoint_workspace)):
         setattr(io, name, None if t is None else t.data_ptr())
     for k, t in out.items():
-        setattr(io, "d" + k, t.data_ptr())
+        if k not in ("S", "uprev"):
+            setattr(io, "d" + k, t.data_ptr())
     flags = ((_cabi.LTV_HAS_K if K is not None else 0) | (_cabi.LTV_HAS_XREF if xref is not None else 0)
              | (_cabi.LTV_HAS_UREF if uref is not None else 0) | (_cabi.LTV_STAGE_WEIGHTS if staged else 0))
     dims = _cabi.LtvDims(batch=B, nx=nx, nu=nu, horizon=N, dtype=_cabi.RQP_F64 if dtype == torch.float64 else _cabi.RQP_F32,
@@ -915,8 +1012,13 @@ def condense_ltv_adjoint_device(Ad, Bd, x0, weights, workspace, adjoint_workspac
     lib = _cabi.load()
     with torch.cuda.device(device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _cabi.check(None, lib.rqp_ltv_condense_adjoint(ctypes.byref(dims), device.index or 0, ctypes.byref(io), stream),
-                    "rqp_ltv_condense_adjoint", handleless=True)
+        if rio is None:
+            _cabi.check(None, lib.rqp_ltv_condense_adjoint(ctypes.byref(dims), device.index or 0, ctypes.byref(io), stream),
+                        "rqp_ltv_condense_adjoint", handleless=True)
+        else:
+            _cabi.check(None, lib.rqp_ltv_condense_adjoint_rate(ctypes.byref(dims), device.index or 0, ctypes.byref(io),
+                                                                ctypes.byref(rio), stream),
+                        "rqp_ltv_condense_adjoint_rate", handleless=True)
     return out
 
 
@@ -954,7 +1056,7 @@ class LTVCondenser(object):
                                     adj=ltv_adjoint_workspace(B, self.nx, self.nu, self.horizon, device),
                                     H=None, A=None,
                                     K=None if self.K is None else torch.as_tensor(self.K, dtype=torch.float64, device=device),
-                                    stamp=0)
+                                    stamp=0, adj_for=(B, device))
         return self._slots[key]
 
     def recondense_outputs(self, slot, B, device, dtype):
@@ -963,6 +1065,13 @@ class LTVCondenser(object):
             slot["H"] = torch.empty((B, self.n, self.n), dtype=dtype, device=device)
             slot["A"] = torch.empty((B, self.m, self.n), dtype=dtype, device=device)
         return slot["H"], slot["A"]
+
+    def rate_adjoint_workspace(self, slot):
+        """The slot's adjoint workspace, grown once to what rqp_ltv_condense_adjoint_rate needs (it serves the plain call too)."""
+        if not slot.get("adj_rate"):
+            B, device = slot["adj_for"]
+            slot["adj"], slot["adj_rate"] = ltv_adjoint_rate_workspace(B, self.nx, self.nu, self.horizon, device), True
+        return slot["adj"]
 
     def release(self):
         """Drop every workspace (the next forward allocates again; a pending backward of an earlier forward must not follow)."""
@@ -1025,7 +1134,8 @@ def condense_ltv_device(Ad, Bd, weights, workspace, c=None, H=None, A=None, S=No
     (then Qf = None for a staged Q), or an ``_LtvStageWeights``, select the stage-weight kernels (RQP_LTV_STAGE_WEIGHTS);
     ``workspace`` from ``ltv_workspace`` carries the maps the vector step needs.  ``H`` / ``A``: optional output tensors.
     ``S``: a rate weight from ``rate_weight_device`` ([B, N, nu, nu] float64 on the device) adds the input-rate cost
-    (C-ABI rqp_ltv_condense_rate); the workspace then serves ``ltv_vectors_device(..., S=, uprev=)`` only, and no adjoint.
+    (C-ABI rqp_ltv_condense_rate); the workspace then serves ``ltv_vectors_device(..., S=, uprev=)`` only, and its adjoint is
+    ``condense_ltv_adjoint_rate_device``.
     Enqueued on the current stream; returns (H, A)."""
     import ctypes
     import torch

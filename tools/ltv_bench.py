@@ -18,10 +18,13 @@ Input-rate columns (--rate): `condense` with a rate weight S [B, N, nu, nu] (rqp
 rqp_ltv_rate_rows and rqp_ltv_rate_bounds written into the tail of [B, m + N nu, ...] tensors; the driver's strided copy of the m
 base rows into that tensor; and update(Hx, Ax) + warm solve() of a BatchedLTVMPC(stage_rows=nc, du_max=) handle (m_c + N nu rows)
 next to the same two of the stage handle (m_c rows).
+Rate-adjoint columns (--rate-adjoint): the reverse mode with the rate terms (condense_ltv_adjoint_rate_device,
+rqp_ltv_condense_adjoint_rate: every cotangent given, the three of the rate rows among them, every gradient wanted, dS and duprev
+among them) next to the plain adjoint of the same build, alternating call by call, on workspaces of its own (rate_adj_* in --out).
 Per-kernel times (k_ltv_transition among them): run the same command under `rocprofv3 --kernel-trace --stats`.
 
-    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--stage-weights] [--rate] [--out profiles/r8_ltv/ltv_bench.json]
-        [--rate-out profiles/r12_ltv_rate/ltv_rate_bench.json]
+    python tools/ltv_bench.py [--reps 20] [--stage-rows 6] [--stage-weights] [--rate] [--rate-adjoint]
+        [--out profiles/r8_ltv/ltv_bench.json] [--rate-out profiles/r12_ltv_rate/ltv_rate_bench.json]
         [--stage-out profiles/r10_ltv_stage/ltv_stage_bench.json] [--stage-weights-out profiles/r11_ltv_stage_cost/ltv_stage_cost_bench.json]
 """
 import argparse
@@ -110,6 +113,8 @@ def main():
     ap.add_argument("--rate", action="store_true",
                     help="add the input-rate columns: condense / vectors with a rate weight, the rate rows and bounds, the base-row copy")
     ap.add_argument("--rate-out", default=os.path.join(REPO, "profiles", "r12_ltv_rate", "ltv_rate_bench.json"))
+    ap.add_argument("--rate-adjoint", action="store_true",
+                    help="add the rate-adjoint columns: rqp_ltv_condense_adjoint_rate alternating with rqp_ltv_condense_adjoint")
     args = ap.parse_args()
     if not NU <= args.stage_rows <= 32:
         ap.error("--stage-rows must be in [%d, 32]: the input box takes %d rows of E, the kernels hold 32" % (NU, NU))
@@ -159,6 +164,22 @@ def main():
         out["condense_adjoint_ms"], out["condense_adjoint_min_ms"], out["condense_adjoint_max_ms"] = _timed(torch, back, args.reps)
         only_x0 = lambda: mpc.condense_ltv_adjoint_device(Adt, Bdt, xt, ctl.weights, buf["ws"], adj_ws, xref=xr, want=("x0",), **cot)
         out["condense_adjoint_x0_only_ms"], _, _ = _timed(torch, only_x0, args.reps)
+        if args.rate_adjoint:                  # the adjoint with the rate terms, alternating with the plain one
+            Sr = _stage_weights(np.random.RandomState(3), B)[1]
+            Sd = mpc.rate_weight_device(Sr, NU, N, B, dev)
+            del Sr
+            ws2, adj2 = mpc.ltv_workspace(B, NX, NU, N, dev), mpc.ltv_adjoint_rate_workspace(B, NX, NU, N, dev)
+            H2, A2 = torch.empty_like(buf["H"]), torch.empty_like(buf["A"])
+            mpc.condense_ltv_device(Adt, Bdt, ctl.weights, ws2, H=H2, A=A2, S=Sd)
+            del H2, A2
+            up = t(0.1 * rs.randn(B, NU))
+            rcot = dict(dA_r=t(rs.randn(B, ctl.n, ctl.n)), dl_r=t(rs.randn(B, ctl.n)), du_r=t(rs.randn(B, ctl.n)))
+            back_r = lambda: mpc.condense_ltv_adjoint_rate_device(Adt, Bdt, xt, ctl.weights, ws2, adj2, Sd, up, xref=xr, **cot, **rcot)
+            a, b = _timed_ab(torch, back, back_r, args.reps)
+            out["rate_adj_ab_plain_ms"], out["rate_adj_ab_plain_min_ms"], out["rate_adj_ab_plain_max_ms"] = a
+            out["rate_adj_ab_rate_ms"], out["rate_adj_ab_rate_min_ms"], out["rate_adj_ab_rate_max_ms"] = b
+            out["rate_adj_rate_minus_plain_ms"] = b[0] - a[0]
+            del Sd, ws2, adj2, up, rcot
         if args.stage_weights:                 # the same three calls with per-(instance, stage) weights, alternating with the shared ones
             Qs, Rs = _stage_weights(np.random.RandomState(2), B)
             sw = mpc._LtvStageWeights(NX, NU, N, Qs, Rs, None, K)
