@@ -475,7 +475,7 @@ __global__ void __launch_bounds__(256) k_factor(SetupArgs a) {
     }
 }
 
-// Large n (142 < n <= 320, e.g. the sparse linear-MPC form n = 320): BLOCKED Gauss-Jordan, 16 pivots per pass over the matrix.
+// Large n (142 <= n <= 320 -- the LDS mode of k_factor ends at 141 -- e.g. the sparse linear-MPC form n = 320): BLOCKED Gauss-Jordan, 16 pivots per pass over the matrix.
 // With M = [[A, B], [C, D]] and pivot block A (16 x 16): M <- [[A^-1, A^-1 B], [-C A^-1, D - C A^-1 B]] -- exactly 16 steps of the
 // unblocked sweep of k_factor, but the matrix (float64, in the L2-resident scratch slab) is read and written ONCE per 16 pivots:
 // column panel C, row panel B and A live in LDS, the trailing update is a rank-16 product from LDS.  1024 threads per matrix,

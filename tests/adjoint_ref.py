@@ -59,12 +59,15 @@ def _matrices(rs, n, n_eq, n_ineq):
     return H, np.vstack((rs.randn(n_eq, n), rs.randn(n_ineq, n)))
 
 
-def margin_qp_batch(B, n, n_eq, n_ineq, seed, shared=False):
+def margin_qp_batch(B, n, n_eq, n_ineq, seed, shared=False, n_active=None):
     """B QPs with a planted solution x, multipliers y and active set with margins: every active multiplier |y| in
     [0.5, 1.5], every inactive slack (on both sides) in [0.5, 1.5], at most n / 2 active rows: fewer than n, so the
     multipliers are unique, and far enough from n that the active rows are well conditioned (an active set of n - 1 random
     rows can be nearly dependent; the regularised solve with its few refinement steps then does not converge).
-    Equality rows (l == u) are active with a random sign of y.  Returns dict H, g, A, l, u, x, y, z, active (numpy;
+    Equality rows (l == u) are active with a random sign of y.  `n_active` (length B, default None: the random sets above,
+    drawn exactly as without the keyword) gives the exact number of active inequality rows of each instance, 0 allowed and
+    at most min(n // 2 - n_eq, n_ineq); with n_eq = 0 and n_active[b] = 0 instance b has an empty active set (y = 0 and
+    l < A x < u).  Returns dict H, g, A, l, u, x, y, z, active (numpy;
     H [n, n] / A [m, n] when shared, else with a leading batch dimension)."""
     rs = np.random.RandomState(seed)
     m = n_eq + n_ineq
@@ -72,12 +75,19 @@ def margin_qp_batch(B, n, n_eq, n_ineq, seed, shared=False):
     Hs, As = _matrices(rs, n, n_eq, n_ineq) if shared else (None, None)
     out = {k: [] for k in ("H", "g", "A", "l", "u", "x", "y", "z", "active")}
     cap = n // 2 - n_eq                                            # active inequality rows allowed
-    for _ in range(B):
+    assert n_active is None or len(n_active) == B
+    for b in range(B):
         H, A = (Hs, As) if shared else _matrices(rs, n, n_eq, n_ineq)
-        side = rs.choice([-1, 0, 1], size=n_ineq, p=[0.25, 0.5, 0.25])
-        on = np.flatnonzero(side)
-        if len(on) > cap:
-            side[rs.permutation(on)[:len(on) - cap]] = 0
+        if n_active is None:
+            side = rs.choice([-1, 0, 1], size=n_ineq, p=[0.25, 0.5, 0.25])
+            on = np.flatnonzero(side)
+            if len(on) > cap:
+                side[rs.permutation(on)[:len(on) - cap]] = 0
+        else:
+            k = int(n_active[b])
+            assert 0 <= k <= min(cap, n_ineq), (k, cap, n_ineq)
+            side = np.zeros(n_ineq, dtype=np.int64)
+            side[rs.permutation(n_ineq)[:k]] = rs.choice([-1, 1], size=k)
         x = rs.randn(n)
         ax = A @ x
         mag = rs.uniform(0.5, 1.5, size=m)
